@@ -12,6 +12,11 @@ Driver contract: rank 0 prints ONE JSON line; timing is bracketed by
 barrier + torch.cuda.synchronize on both sides; value is the whole-job
 aggregate (max elapsed over ranks).  --path client bypasses FUSE and reads
 via the in-process client (plumbing mode / containers without /dev/fuse).
+
+A plain run sets up, warms up, times --steps steps and prints the result
+line.  --dump-outputs DIR also saves a fixed seeded sample of the bytes the
+last timed step delivered (same arguments -> same inputs -> comparable
+across builds).  --full is the switch for secondary measurements.
 """
 from __future__ import annotations
 
@@ -31,8 +36,79 @@ REFERENCE_PEAK_GIBPS = 9.5     # 256 KiB seq read, 32 threads
 REFERENCE_PEAK_RAND_GIBPS = 9.0
 
 
+DUMP_SAMPLE_BYTES = 64 << 10   # one sampled extent of a sequential file
+DUMP_MAX_EXTENTS = 128         # 128 x 64 KiB x float32 = 32 MiB on disk
+DUMP_RAND_OPS = 16             # 4 KiB reads kept per randread4k thread
+
+
 def log(rank, *a):
     print(f"[bench r{rank}]", *a, file=sys.stderr, flush=True)
+
+
+class OutputCapture:
+    """--dump-outputs: a fixed, seeded sample of the bytes the timed path
+    handed its caller in the LAST timed step.  Sequential workloads keep
+    DUMP_SAMPLE_BYTES-long extents at seeded (file, offset) positions;
+    randread4k keeps the first reads of every thread, up to DUMP_RAND_OPS
+    or as many as the shortest thread issued (their offsets are seeded per
+    thread, so they repeat from run to run).  Each thread fills rows of
+    its own, so no lock is needed."""
+
+    def __init__(self, args, rank):
+        import random
+        import numpy as np
+        self.np = np
+        self.workload = args.workload
+        if args.workload == "randread4k":
+            self.rows = np.zeros((args.threads, DUMP_RAND_OPS, 4096),
+                                 dtype=np.uint8)
+            self.filled = np.zeros((args.threads, DUMP_RAND_OPS),
+                                   dtype=np.int64)
+            self.want = 4096
+            return
+        rng = random.Random(0x5EED + rank)
+        self.want = min(DUMP_SAMPLE_BYTES, args.file_size)
+        n = min(args.files * 4, DUMP_MAX_EXTENTS)
+        self.rows = np.zeros((n, self.want), dtype=np.uint8)
+        self.filled = np.zeros(n, dtype=np.int64)
+        self.extents: dict[int, list[tuple[int, int]]] = {}
+        for row in range(n):
+            off = rng.randrange(args.file_size - self.want + 1)
+            self.extents.setdefault(row % args.files, []).append((off, row))
+
+    def take(self, i, pos, view):
+        """`view` holds bytes [pos, pos + len(view)) of file i."""
+        end = pos + len(view)
+        for off, row in self.extents.get(i, ()):
+            lo, hi = max(off, pos), min(off + self.want, end)
+            if lo < hi:
+                self.rows[row, lo - off:hi - off] = self.np.frombuffer(
+                    view, dtype=self.np.uint8)[lo - pos:hi - pos]
+                self.filled[row] += hi - lo
+
+    def take_rand(self, t, j, view):
+        """`view` holds the j-th 4 KiB read of thread t."""
+        self.rows[t, j, :len(view)] = self.np.frombuffer(
+            view, dtype=self.np.uint8)
+        self.filled[t, j] += len(view)
+
+    def save(self, out_dir, rank):
+        if self.workload == "randread4k":
+            # a step issues the same number of reads on every thread
+            k = int((self.filled != 0).all(axis=0).sum())
+            if k == 0:
+                raise RuntimeError("--dump-outputs: the last timed step "
+                                   "issued no read on some thread")
+            self.rows, self.filled = self.rows[:, :k], self.filled[:, :k]
+        if (self.filled != self.want).any():
+            raise RuntimeError(
+                "--dump-outputs: the last timed step did not deliver every "
+                f"sampled extent ({int((self.filled != self.want).sum())} "
+                "incomplete)")
+        os.makedirs(out_dir, exist_ok=True)
+        dest = os.path.join(out_dir, f"{self.workload}_r{rank}.npy")
+        self.np.save(dest, self.rows.astype(self.np.float32))
+        return dest
 
 
 class ClusterRuntime:
@@ -193,7 +269,7 @@ def write_dataset(args, rank, rt, mnt):
 # workloads
 # ---------------------------------------------------------------------------
 
-def step_fuse_seq(args, rank, mnt) -> int:
+def step_fuse_seq(args, rank, mnt, cap=None) -> int:
     """T threads, each sequentially reading its share of files in
     read_chunk chunks through the kernel mount."""
     paths = [f"{mnt}/bench/r{rank}/f{i}" for i in range(args.files)]
@@ -206,11 +282,15 @@ def step_fuse_seq(args, rank, mnt) -> int:
             mv = memoryview(buf)
             for i in range(t, len(paths), args.threads):
                 fd = os.open(paths[i], os.O_RDONLY)
+                pos = 0
                 try:
                     while True:
                         n = os.readv(fd, [mv])
                         if n <= 0:
                             break
+                        if cap is not None:
+                            cap.take(i, pos, mv[:n])
+                        pos += n
                         total[t] += n
                 finally:
                     os.close(fd)
@@ -232,7 +312,7 @@ def step_fuse_seq(args, rank, mnt) -> int:
     return got
 
 
-def step_fuse_rand4k(args, rank, mnt, lat_out: list) -> int:
+def step_fuse_rand4k(args, rank, mnt, lat_out: list, cap=None) -> int:
     """T threads x N random 4 KiB preads (the IOPS path)."""
     paths = [f"{mnt}/bench/r{rank}/f{i}" for i in range(args.files)]
     import random
@@ -246,12 +326,14 @@ def step_fuse_rand4k(args, rank, mnt, lat_out: list) -> int:
             rng = random.Random(t * 7919 + rank)
             fds = [os.open(p, os.O_RDONLY) for p in paths]
             try:
-                for _ in range(per_thread):
+                for j in range(per_thread):
                     fd = fds[rng.randrange(len(fds))]
                     off = rng.randrange(max(1, args.file_size - 4096))
                     t0 = time.perf_counter_ns()
                     data = os.pread(fd, 4096, off)
                     lats[t].append((time.perf_counter_ns() - t0) / 1000.0)
+                    if cap is not None and j < cap.rows.shape[1]:
+                        cap.take_rand(t, j, data)
                     total[t] += len(data)
             finally:
                 for fd in fds:
@@ -285,7 +367,8 @@ def _sync_readers(args, rank, rt):
     return readers
 
 
-def step_client_seq_remote(args, rank, rt, disable_sc: bool = True) -> int:
+def step_client_seq_remote(args, rank, rt, disable_sc: bool = True,
+                           cap=None) -> int:
     """Sequential reads with short-circuit DISABLED: every byte crosses
     the worker's streaming RPC (the inter-node data plane, exercised
     over loopback — one concurrent stream per file)."""
@@ -295,7 +378,7 @@ def step_client_seq_remote(args, rank, rt, disable_sc: bool = True) -> int:
         readers = [await rt.fs.open(f"/bench/r{rank}/f{i}")
                    for i in range(args.files)]
 
-        async def read_file(r):
+        async def read_file(i, r):
             buf = bytearray(args.read_chunk)
             pos = 0
             while pos < r.length:
@@ -303,10 +386,13 @@ def step_client_seq_remote(args, rank, rt, disable_sc: bool = True) -> int:
                 got = await r.pread_into(pos, buf, 0, want)
                 if got <= 0:
                     break
+                if cap is not None:
+                    cap.take(i, pos, memoryview(buf)[:got])
                 pos += got
             return pos
         try:
-            totals = await asyncio.gather(*(read_file(r) for r in readers))
+            totals = await asyncio.gather(
+                *(read_file(i, r) for i, r in enumerate(readers)))
         finally:
             for r in readers:
                 r.close()
@@ -315,7 +401,7 @@ def step_client_seq_remote(args, rank, rt, disable_sc: bool = True) -> int:
     return rt.call(run())
 
 
-def step_client_rand4k(args, rank, rt, lat_out: list) -> int:
+def step_client_rand4k(args, rank, rt, lat_out: list, cap=None) -> int:
     """Random 4 KiB reads via the SYNC short-circuit path: plain OS
     threads, no event loop in the per-op path (this is the IOPS metric)."""
     import random
@@ -335,6 +421,8 @@ def step_client_rand4k(args, rank, rt, lat_out: list) -> int:
             pbuf = native.PinnedBuffer(4096 * depth) if use_pinned else None
             buf = bytearray(4096) if pbuf is None else None
             batches = per_thread // depth
+            keep = cap.rows.shape[1] if cap is not None else 0
+            done = 0   # 4 KiB reads this thread has finished
             for _ in range(max(1, batches)):
                 r = readers[rng.randrange(len(readers))]
                 t0 = time.perf_counter_ns()
@@ -352,6 +440,12 @@ def step_client_rand4k(args, rank, rt, lat_out: list) -> int:
                 # latency per IO (batch wall / depth, the fio convention)
                 lats[t].append((time.perf_counter_ns() - t0) / 1000.0 / depth)
                 total[t] += n
+                if done < keep:
+                    got = pbuf.view if pbuf is not None else memoryview(buf)
+                    for k in range(min(n // 4096, keep - done)):
+                        cap.take_rand(t, done + k,
+                                      got[k * 4096:(k + 1) * 4096])
+                done += n // 4096
             if pbuf is not None:
                 pbuf.close()
         except Exception as e:  # noqa: BLE001
@@ -375,7 +469,7 @@ def step_client_rand4k(args, rank, rt, lat_out: list) -> int:
     return sum(total)
 
 
-def step_client_seq(args, rank, rt) -> int:
+def step_client_seq(args, rank, rt, cap=None) -> int:
     """Sequential reads via the SYNC short-circuit path: OS threads with
     pinned destination buffers (direct D2H DMA, no event loop per op).
     Covers in-process registry hits AND hipIpc-mapped other-process
@@ -386,7 +480,8 @@ def step_client_seq(args, rank, rt) -> int:
     try:
         readers = _sync_readers(args, rank, rt)
     except Exception:
-        return step_client_seq_remote(args, rank, rt, disable_sc=False)
+        return step_client_seq_remote(args, rank, rt, disable_sc=False,
+                                      cap=cap)
     nthreads = min(args.threads, max(1, len(readers)))
     total = [0] * nthreads
     errs = []
@@ -411,6 +506,8 @@ def step_client_seq(args, rank, rt) -> int:
                                 for k in range(depth)]
                         r.pread_batch_ptr(offs, args.read_chunk, pbuf.ptr,
                                           args.read_chunk)
+                        if cap is not None:
+                            cap.take(i, pos, pbuf.view)
                         pos += args.read_chunk * depth
                         total[t] += args.read_chunk * depth
                         continue
@@ -421,6 +518,9 @@ def step_client_seq(args, rank, rt) -> int:
                         n = r.pread_into(pos, buf, 0, want)
                     if n <= 0:
                         break
+                    if cap is not None:
+                        cap.take(i, pos, (pbuf.view if pbuf is not None
+                                          else memoryview(buf))[:n])
                     pos += n
                     total[t] += n
             if pbuf is not None:
@@ -503,6 +603,28 @@ def step_fuse_seqwrite(args, rank, mnt) -> int:
     if errs:
         raise errs[0]
     return sum(total)
+
+
+def capture_written(args, rank, rt, cap) -> None:
+    """seqwrite's output is the files themselves: read the sampled extents
+    of what the last timed step wrote back through the client."""
+    async def run():
+        for i, extents in cap.extents.items():
+            r = await rt.fs.open(f"/bench/r{rank}/w{i}")
+            try:
+                buf = bytearray(cap.want)
+                for off, _row in extents:
+                    got = 0
+                    while got < cap.want:
+                        n = await r.pread_into(off + got, buf, got,
+                                               cap.want - got)
+                        if n <= 0:
+                            break
+                        got += n
+                    cap.take(i, off, memoryview(buf)[:got])
+            finally:
+                r.close()
+    rt.call(run())
 
 
 def run_scale_sweep(args, rank, world, dist, torch, rt, has_gpu,
@@ -625,7 +747,19 @@ def main():
                         "weak-scaling curve over rank subgroups plus a "
                         "BlockDistributor.broadcast_file xGMI benchmark, "
                         "writing profiles/scale_sweep_n<world>.json")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write a fixed seeded "
+                        "sample of the bytes the last timed step delivered "
+                        "to DIR/<workload>_r<rank>.npy (float32)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements and checks; "
+                        "a plain run only sets up, warms up, times --steps "
+                        "steps and prints the result line (today every "
+                        "secondary measurement already sits behind a "
+                        "switch of its own, e.g. --scale-sweep)")
     args = p.parse_args()
+    if args.dump_outputs and args.steps < 1:
+        p.error("--dump-outputs needs at least one timed step")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -718,30 +852,37 @@ def _run_bench(args, rank, world, dist, torch, rt, mnt, has_gpu,
 
     lat_out: list = []
 
-    def one_step():
+    def one_step(cap=None):
         if args.workload == "seqwrite":
             if args.path == "fuse":
                 return step_fuse_seqwrite(args, rank, mnt)
             return step_client_seqwrite(args, rank, rt)
         if args.workload == "randread4k":
             if args.path != "fuse":
-                return step_client_rand4k(args, rank, rt, lat_out)
-            return step_fuse_rand4k(args, rank, mnt, lat_out)
+                return step_client_rand4k(args, rank, rt, lat_out, cap)
+            return step_fuse_rand4k(args, rank, mnt, lat_out, cap)
         if args.path == "fuse":
-            return step_fuse_seq(args, rank, mnt)
+            return step_fuse_seq(args, rank, mnt, cap)
         if args.no_short_circuit:
-            return step_client_seq_remote(args, rank, rt)
-        return step_client_seq(args, rank, rt)
+            return step_client_seq_remote(args, rank, rt, cap=cap)
+        return step_client_seq(args, rank, rt, cap)
 
+    cap = OutputCapture(args, rank) if args.dump_outputs else None
     for _ in range(args.warmup):
         one_step()
     barrier_sync()
     t_start = time.perf_counter()
     bytes_per_step = 0
-    for _ in range(args.steps):
-        bytes_per_step = one_step()
+    for s in range(args.steps):
+        # the read workloads copy their sampled extents in the last step
+        bytes_per_step = one_step(cap if s == args.steps - 1 else None)
     barrier_sync()
     elapsed = time.perf_counter() - t_start
+
+    if cap is not None:
+        if args.workload == "seqwrite":
+            capture_written(args, rank, rt, cap)
+        log(rank, f"outputs written to {cap.save(args.dump_outputs, rank)}")
 
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64)
