@@ -1003,7 +1003,8 @@ static py::list reader_pread_batch(int64_t rid,
 }
 
 // ---------------------------------------------------------------------------
-// LZ4 container: compress/decompress (host) + decompress-into-arena (GPU)
+// LZ4 container: compress/decompress (host) + compress-from-arena and
+// decompress-into-arena (GPU)
 // ---------------------------------------------------------------------------
 
 static py::bytes lz4_compress_py(py::buffer buf) {
@@ -1057,6 +1058,15 @@ static Lz4Header lz4_parse(const uint8_t* p, size_t n) {
   if (n < 20 + 4ull * h.n_chunks) throw std::runtime_error("lz4: truncated");
   h.sizes = (const uint32_t*)(p + 20);
   h.payload = p + 20 + 4ull * h.n_chunks;
+  // the decoders walk sizes[] over the payload and index chunk c at
+  // c * chunk_size: both must stay inside what the header announces
+  uint64_t payload_n = 0;
+  for (uint32_t c = 0; c < h.n_chunks; ++c) payload_n += h.sizes[c];
+  if (payload_n > n - 20 - 4ull * h.n_chunks)
+    throw std::runtime_error("lz4: truncated");
+  if ((uint64_t)h.n_chunks * h.chunk_size < h.raw_size ||
+      (h.n_chunks && (uint64_t)(h.n_chunks - 1) * h.chunk_size >= h.raw_size))
+    throw std::runtime_error("lz4: chunk table does not match raw size");
   return h;
 }
 
@@ -1141,6 +1151,110 @@ static uint64_t arena_lz4_decompress(int ah, uint64_t dst_off, py::buffer buf) {
   if (err_host) throw std::runtime_error(
       "lz4: corrupt chunk " + std::to_string(err_host - 1) + " (device)");
   return h.raw_size;
+}
+
+// compress arena bytes [off, off+n) into a CVLZ container.  Device arenas:
+// one wave per 64K chunk compresses into fixed-stride scratch slots, the
+// chunk lengths come back in one small D2H, copy_extents_kernel packs the
+// payloads contiguously on the device and ONE D2H moves them — only
+// compressed bytes cross the host link.
+static py::bytes arena_lz4_compress(int ah, uint64_t off, uint64_t n) {
+  Arena* a = get_arena(ah);
+  check_range(a, off, n);
+  if (n > LZ4_DEVICE_MAX_N)
+    throw std::runtime_error(
+        "lz4: compress of " + std::to_string(n) + " bytes exceeds the " +
+        std::to_string(LZ4_DEVICE_MAX_N) + "-byte per-call limit; segment it");
+  uint32_t n_chunks = (uint32_t)((n + LZ4_CHUNK - 1) / LZ4_CHUNK);
+  size_t header = 20 + 4ull * n_chunks;
+  std::vector<uint32_t> sizes(n_chunks);
+  std::vector<uint8_t> out(header);
+  {
+    py::gil_scoped_release rel;
+    if (!a->is_dev()) {
+      std::vector<uint8_t> tmp(LZ4_SLOT_STRIDE);
+      const uint8_t* src = (const uint8_t*)a->base + off;
+      for (uint32_t c = 0; c < n_chunks; ++c) {
+        size_t cn = std::min<size_t>(LZ4_CHUNK, n - (size_t)c * LZ4_CHUNK);
+        size_t cs = lz4_compress_block(src + (size_t)c * LZ4_CHUNK, cn,
+                                       tmp.data());
+        sizes[c] = (uint32_t)cs;
+        out.insert(out.end(), tmp.data(), tmp.data() + cs);
+      }
+    } else if (n_chunks) {
+      std::lock_guard<std::mutex> g(a->mu);
+      HIP_CHECK(hipSetDevice(a->device));
+      // scratch: slots | packed payload | lens | err | extent + tile tables
+      size_t slots_n = (size_t)n_chunks * LZ4_SLOT_STRIDE;
+      size_t max_tiles = 2ull * n_chunks;   // a slot spans at most 2 tiles
+      size_t meta = 4ull * n_chunks + 64 + n_chunks * sizeof(Extent) +
+                    max_tiles * (sizeof(uint32_t) + sizeof(uint64_t)) + 64;
+      ensure_scratch(a, 2 * slots_n + meta);
+      uint8_t* d_slots = (uint8_t*)a->scratch;
+      uint8_t* d_pack = d_slots + slots_n;
+      uint32_t* d_len = (uint32_t*)(d_pack + slots_n);
+      int* d_err = (int*)(d_len + n_chunks);
+      Extent* d_ext = (Extent*)(((uintptr_t)(d_err + 1) + 63) & ~63ull);
+      uint32_t* d_te = (uint32_t*)(d_ext + n_chunks);
+      uint64_t* d_to = (uint64_t*)(((uintptr_t)(d_te + max_tiles) + 7) & ~7ull);
+      HIP_CHECK(hipMemsetAsync(d_err, 0, 4, a->kstream));
+      int grid = (int)std::min<uint32_t>(n_chunks, 16384);
+      (void)hipGetLastError();   // clear stale per-thread state
+      hipLaunchKernelGGL(lz4_compress_kernel, dim3(grid), dim3(64), 0,
+                         a->kstream, (const uint8_t*)a->base, off, n,
+                         (uint32_t)LZ4_CHUNK, d_slots, LZ4_SLOT_STRIDE, d_len,
+                         n_chunks, d_err);
+      HIP_CHECK(hipGetLastError());
+      // lens + error flag are adjacent: one small D2H
+      std::vector<uint32_t> lens(n_chunks + 1);
+      HIP_CHECK(hipMemcpyAsync(lens.data(), d_len, 4ull * (n_chunks + 1),
+                               hipMemcpyDeviceToHost, a->kstream));
+      HIP_CHECK(hipStreamSynchronize(a->kstream));
+      if (lens[n_chunks]) throw std::runtime_error(
+          "lz4: compress slot overflow in chunk " +
+          std::to_string(lens[n_chunks] - 1) + " (device)");
+      std::vector<Extent> exts(n_chunks);
+      std::vector<uint32_t> tile_ext;
+      std::vector<uint64_t> tile_off;
+      uint64_t total = 0;
+      for (uint32_t c = 0; c < n_chunks; ++c) {
+        if (lens[c] == 0 || lens[c] > LZ4_SLOT_STRIDE)
+          throw std::runtime_error("lz4: bad device chunk length");
+        sizes[c] = lens[c];
+        exts[c] = {(uint64_t)c * LZ4_SLOT_STRIDE, total, lens[c]};
+        for (uint64_t t = 0; t < lens[c]; t += TILE) {
+          tile_ext.push_back(c);
+          tile_off.push_back(t);
+        }
+        total += lens[c];
+      }
+      HIP_CHECK(hipMemcpyAsync(d_ext, exts.data(), exts.size() * sizeof(Extent),
+                               hipMemcpyHostToDevice, a->kstream));
+      HIP_CHECK(hipMemcpyAsync(d_te, tile_ext.data(),
+                               tile_ext.size() * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, a->kstream));
+      HIP_CHECK(hipMemcpyAsync(d_to, tile_off.data(),
+                               tile_off.size() * sizeof(uint64_t),
+                               hipMemcpyHostToDevice, a->kstream));
+      hipLaunchKernelGGL(copy_extents_kernel,
+                         dim3((int)std::min<size_t>(tile_ext.size(), 8192)),
+                         dim3(WG), 0, a->kstream, (const uint8_t*)d_slots,
+                         d_pack, d_ext, d_te, d_to, (uint32_t)tile_ext.size());
+      HIP_CHECK(hipGetLastError());
+      out.resize(header + total);
+      HIP_CHECK(hipMemcpyAsync(out.data() + header, d_pack, total,
+                               hipMemcpyDeviceToHost, a->kstream));
+      HIP_CHECK(hipStreamSynchronize(a->kstream));
+    }
+    uint8_t* h = out.data();
+    memcpy(h, &LZ4_MAGIC, 4);
+    memcpy(h + 4, &n, 8);
+    uint32_t ck = LZ4_CHUNK;
+    memcpy(h + 12, &ck, 4);
+    memcpy(h + 16, &n_chunks, 4);
+    memcpy(h + 20, sizes.data(), 4ull * n_chunks);
+  }
+  return py::bytes((const char*)out.data(), out.size());
 }
 
 // ---------------------------------------------------------------------------
@@ -1382,6 +1496,7 @@ PYBIND11_MODULE(_native, m) {
   m.def("lz4_compress", &lz4_compress_py);
   m.def("lz4_decompress", &lz4_decompress_py);
   m.def("arena_lz4_decompress", &arena_lz4_decompress);
+  m.def("arena_lz4_compress", &arena_lz4_compress);
   m.def("crc32c", &crc32c_buf, py::arg("buf"), py::arg("init") = 0);
   m.def("crc32c_combine", &crc32c_combine);
   m.attr("CRC_SUB") = CRC_SUB;

@@ -251,6 +251,70 @@ class BlockWriterRemote:
             self.stream.close()
 
 
+class BlockWriterLz4Remote:
+    """Streaming WriteBlockLz4: each segment goes as a CVLZ container
+    (codec "cvlz", decompressed on the target straight into the block —
+    on its GPU for HBM) or raw (codec "raw", incompressible data).
+    Always the asyncio stream: the native write session stores payloads
+    as they come and must not see a container."""
+
+    WINDOW = 4
+
+    def __init__(self, addr: WorkerAddress, block_id: int, reserve: int,
+                 tier: str):
+        self.addr = addr
+        self.block_id = block_id
+        self.reserve = reserve
+        self.tier = tier
+        self.stream: Optional[RpcStream] = None
+        self.inflight = 0
+        self.wire_bytes = 0
+
+    async def _ensure_open(self) -> None:
+        if self.stream is not None:
+            return
+        client = await factory().get(self.addr.hostname, self.addr.rpc_port)
+        self.stream = client.stream(RpcCode.WriteBlockLz4)
+        await self.stream.call(
+            {"block_id": self.block_id, "reserve": self.reserve,
+             "tier": self.tier}, status=Status.Open)
+
+    async def write_segment(self, data, codec: str) -> None:
+        if codec not in ("cvlz", "raw"):
+            raise err.InvalidArgument(f"unknown codec {codec!r}")
+        await self._ensure_open()
+        await self.stream.send({"codec": codec}, data, Status.Running)
+        self.inflight += 1
+        self.wire_bytes += len(data)
+        while self.inflight >= self.WINDOW:
+            await self.stream.recv()
+            self.inflight -= 1
+
+    async def commit(self, length: int, crc32c: int | None = None) -> str:
+        await self._ensure_open()
+        while self.inflight > 0:
+            await self.stream.recv()
+            self.inflight -= 1
+        hdr = {"length": length}
+        if crc32c is not None:
+            hdr["crc32c"] = crc32c
+        await self.stream.send(hdr, b"", Status.Complete)
+        reply = await self.stream.recv()
+        self.stream.close()
+        self.stream = None
+        self.last_crc = reply.header.get("crc32c")
+        return reply.header.get("tier", "")
+
+    async def abort(self) -> None:
+        if self.stream is not None:
+            try:
+                await self.stream.send({}, b"", Status.Cancel)
+            except Exception:  # noqa: BLE001
+                pass
+            self.stream.close()
+            self.stream = None
+
+
 def make_block_writer(addr: WorkerAddress, block_id: int, reserve: int,
                       tier: str, reopen: bool = False):
     from curvine_amd.worker import registry

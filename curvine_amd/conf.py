@@ -173,9 +173,21 @@ class WorkerConf:
     # the asyncio RpcServer when the extension is unavailable
     native_data: bool = True
     data_threads: int = 12
+    # codec of the replication push: "" = raw bytes, "lz4" = compress on
+    # the source (HIP kernel for HBM blocks), decompress on the target
+    # straight into the new block's extent
+    replication_codec: str = ""
+
+    REPLICATION_CODECS = ("", "lz4")
 
     def parsed_dirs(self) -> list[DataDir]:
         return [DataDir.parse(s) for s in self.data_dirs]
+
+    def validate(self) -> None:
+        if self.replication_codec not in self.REPLICATION_CODECS:
+            raise ValueError(
+                f"unknown worker.replication_codec "
+                f"{self.replication_codec!r} (expected '' or 'lz4')")
 
 
 @dataclass
@@ -294,6 +306,7 @@ class ClusterConf:
             else:
                 setattr(conf, section, value)
         conf.apply_env()
+        conf.worker.validate()
         return conf
 
     @staticmethod

@@ -64,6 +64,34 @@ class OpStats:
         return out
 
 
+class Counters:
+    """Named monotonic counters of one service instance, exported as
+    `curvine_<service>_<name>` on /metrics and as JSON (worker_metrics.rs
+    counter analog).  A fixed name list keeps typos from minting metrics."""
+
+    def __init__(self, names: tuple[str, ...]):
+        self._v = {n: 0 for n in names}
+        self._lock = threading.Lock()
+
+    def inc(self, name: str, n: int = 1) -> None:
+        with self._lock:
+            self._v[name] += n
+
+    def get(self, name: str) -> int:
+        with self._lock:
+            return self._v[name]
+
+    def snapshot(self) -> dict[str, int]:
+        with self._lock:
+            return dict(self._v)
+
+
+# replication push accounting (worker): raw block bytes pushed, bytes that
+# actually crossed the wire, and how many segments went compressed vs raw
+WORKER_COUNTERS = ("replication_raw_bytes", "replication_wire_bytes",
+                   "replication_lz4_segments", "replication_raw_segments")
+
+
 class SpeedCounter:
     """Windowed throughput meter (runtime SpeedCounter analog)."""
 

@@ -147,6 +147,17 @@ class Arena:
         hop); host arena requires a host dst (memcpy)."""
         self._n.arena_gather_ptr(self.handle, triples, dst_ptr)
 
+    def lz4_compress(self, off: int, n: int) -> bytes:
+        """Compress arena bytes [off, off+n) into a CVLZ container (HIP
+        kernel on device arenas: only compressed bytes cross D2H; host
+        codec on host arenas).  At most 16 MiB per call."""
+        return self._n.arena_lz4_compress(self.handle, off, n)
+
+    def lz4_decompress_into(self, off: int, container) -> int:
+        """Decompress a CVLZ container into the arena at `off` (HIP kernel
+        on device arenas); returns the raw size."""
+        return self._n.arena_lz4_decompress(self.handle, off, container)
+
     def base_ptr(self) -> int:
         return self._n.arena_base_ptr(self.handle)
 

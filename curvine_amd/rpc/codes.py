@@ -99,3 +99,4 @@ class RpcCode(IntEnum):
     UnpinBlock = 101           # release a ShortCircuitInfo pin lease
     DeviceShortCircuit = 101   # hipIpc/dmabuf handle for cross-process GPU read
     RcclGroupSetup = 102       # establish an RCCL communicator for bulk distribution
+    WriteBlockLz4 = 103        # WriteBlock stream whose segments may be CVLZ containers

@@ -191,6 +191,8 @@ class WebServer:
             if path == "/api/storage" and self.worker:
                 return self._json([s.__dict__
                                    for s in self.worker.store.storages()])
+            if path == "/api/worker-counters" and self.worker:
+                return self._json(self.worker.counters.snapshot())
             if path == "/api/fuse" and self.fuse_session:
                 return self._json(self.fuse_session.stats())
             if path == "/metrics":
@@ -222,6 +224,8 @@ class WebServer:
                 lines.append(f"curvine_worker_capacity_bytes{lbl} {s.capacity}")
                 lines.append(f"curvine_worker_used_bytes{lbl} {s.used}")
                 lines.append(f"curvine_worker_blocks{lbl} {s.block_num}")
+            for k, v in self.worker.counters.snapshot().items():
+                lines.append(f"curvine_worker_{k} {v}")
             stats_fn = getattr(self.worker.rpc, "stats", None)
             if stats_fn:
                 try:

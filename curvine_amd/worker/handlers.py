@@ -70,6 +70,8 @@ class WorkerHandler:
         code = msg.code
         if code == int(RpcCode.WriteBlock):
             return await self._write_block(msg)
+        if code == int(RpcCode.WriteBlockLz4):
+            return await self._write_block_lz4(msg)
         if code == int(RpcCode.ReadBlock):
             return await self._read_block(msg, conn)
         if code == int(RpcCode.WriteBlocksBatch):
@@ -148,6 +150,72 @@ class WorkerHandler:
         if msg.req_status == Status.Cancel:
             await loop.run_in_executor(None, self.store.abort, sess["block_id"])
             self.writes.pop(msg.req_id, None)
+            return msg.reply({}, resp_status=Status.Complete)
+        raise err.InvalidArgument(f"write stream status {msg.req_status}")
+
+    async def _write_block_lz4(self, msg: Message) -> Message:
+        """WriteBlock-shaped stream whose Running frames carry one segment
+        each, as a CVLZ container ({codec: "cvlz"}, decompressed straight
+        into the block — on the GPU for HBM) or raw ({codec: "raw"}).
+        Sessions live in `self.writes`, so a dropped connection aborts them
+        in on_close; any failure aborts the block so no extent stays
+        allocated."""
+        loop = asyncio.get_event_loop()
+        if msg.req_status == Status.Open:
+            h = msg.header
+            writer = await loop.run_in_executor(
+                None, self.store.create_writer, h["block_id"],
+                h.get("reserve", 64 << 20), h.get("tier", ""))
+            self.writes[msg.req_id] = {"writer": writer,
+                                       "block_id": h["block_id"],
+                                       "reopen": False,
+                                       "t0": time.perf_counter()}
+            return msg.reply({"ok": True}, resp_status=Status.Running)
+        sess = self.writes.get(msg.req_id)
+        if sess is None:
+            raise err.FsError("write stream not open")
+        bid = sess["block_id"]
+        if msg.req_status == Status.Running:
+            try:
+                codec = msg.header.get("codec")
+                if codec == "cvlz":
+                    await loop.run_in_executor(None, sess["writer"].write_lz4,
+                                               msg.data)
+                elif codec == "raw":
+                    if msg.data:
+                        w = sess["writer"]
+                        if w.pos + len(msg.data) > w.meta["reserved"]:
+                            raise err.InvalidArgument(
+                                "raw segment passes the block's reservation")
+                        await loop.run_in_executor(None, w.write, msg.data)
+                else:
+                    raise err.InvalidArgument(f"unknown codec {codec!r}")
+            except Exception:
+                self.writes.pop(msg.req_id, None)
+                await loop.run_in_executor(None, self.store.abort, bid)
+                raise
+            return msg.reply({}, resp_status=Status.Running)
+        if msg.req_status == Status.Complete:
+            self.writes.pop(msg.req_id, None)
+            try:
+                length = msg.header.get("length", sess["writer"].pos)
+                tier = await loop.run_in_executor(
+                    None, self.store.finalize, bid, length)
+            except Exception:
+                await loop.run_in_executor(None, self.store.abort, bid)
+                raise
+            crc = self.store.block_crc(bid)
+            want = msg.header.get("crc32c")
+            if want is not None and crc != want:
+                await loop.run_in_executor(None, self.store.delete, bid)
+                raise err.ChecksumMismatch(
+                    f"block {bid}: sender crc32c {want:#x}, stored "
+                    f"{'none' if crc is None else hex(crc)}")
+            return msg.reply({"tier": tier, "crc32c": crc},
+                             resp_status=Status.Complete)
+        if msg.req_status == Status.Cancel:
+            self.writes.pop(msg.req_id, None)
+            await loop.run_in_executor(None, self.store.abort, bid)
             return msg.reply({}, resp_status=Status.Complete)
         raise err.InvalidArgument(f"write stream status {msg.req_status}")
 

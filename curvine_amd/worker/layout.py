@@ -19,6 +19,21 @@ from curvine_amd.conf import DataDir, TIER_HBM, TIER_MEM
 from curvine_amd.native import Arena
 
 
+_LZ4_MAGIC = 0x435A4C34   # CVLZ container (csrc/lz4.hip)
+LZ4_MAX_SEGMENT = 16 << 20   # Arena.lz4_compress per-call limit
+
+
+def lz4_raw_size(container) -> int:
+    """raw_size field of a CVLZ container header."""
+    import struct
+    if len(container) < 20:
+        raise err.InvalidArgument("lz4: short container")
+    magic, raw = struct.unpack_from("<IQ", container, 0)
+    if magic != _LZ4_MAGIC:
+        raise err.InvalidArgument("lz4: bad magic")
+    return raw
+
+
 class BlockWriter:
     """Append-only writer for one block."""
 
@@ -47,6 +62,21 @@ class BlockWriter:
         self.layout._write_at(self.meta, off, data, n)
         self.pos = max(self.pos, off + n)
         return n
+
+    def write_lz4(self, container) -> int:
+        """Append a CVLZ container: decompressed at `pos` (on the GPU for
+        HBM blocks); returns the raw size.  Refused before any byte is
+        written when the raw size would pass the reservation."""
+        raw = lz4_raw_size(container)
+        if self.pos + raw > self.meta["reserved"]:
+            raise err.InvalidArgument(
+                f"lz4 segment of {raw} raw bytes at {self.pos} passes the "
+                f"block's reservation {self.meta['reserved']}")
+        got = self.layout._write_lz4_at(self.meta, self.pos, container)
+        if got != raw:
+            raise err.FsError(f"lz4 segment decoded {got} of {raw} bytes")
+        self.pos += raw
+        return raw
 
 
 class BlockReader:
@@ -77,6 +107,16 @@ class BlockReader:
 
     def crc32c(self, off: int, n: int) -> int:
         return self.layout._crc(self.meta, off, min(n, self.length - off))
+
+    def read_lz4(self, off: int, n: int) -> bytes:
+        """[off, off+n) as a CVLZ container (compressed on the GPU for HBM
+        blocks, so only compressed bytes cross to the host).  At most
+        LZ4_MAX_SEGMENT raw bytes per call."""
+        n = max(0, min(n, self.length - off))
+        if n > LZ4_MAX_SEGMENT:
+            raise err.InvalidArgument(
+                f"lz4 segment of {n} bytes exceeds {LZ4_MAX_SEGMENT}")
+        return self.layout._read_lz4(self.meta, off, n)
 
     def close(self) -> None:
         pass
@@ -132,6 +172,19 @@ class BlockLayout:
 
     def _crc(self, meta: dict, off: int, n: int) -> int:
         raise NotImplementedError
+
+    # LZ4 segments: the defaults stage raw bytes on the host and use the
+    # host codec; ArenaLayout overrides both with the arena calls
+    def _read_lz4(self, meta: dict, off: int, n: int) -> bytes:
+        from curvine_amd.native import lz4_compress
+        return lz4_compress(self._read_at(meta, off, n) if n else b"")
+
+    def _write_lz4_at(self, meta: dict, off: int, container) -> int:
+        from curvine_amd.native import lz4_decompress
+        raw = lz4_decompress(container)
+        if raw:
+            self._write_at(meta, off, raw, len(raw))
+        return len(raw)
 
     def local_info(self, meta: dict) -> dict:
         """Short-circuit disclosure (block_store.rs:253-271 analog)."""
@@ -189,6 +242,12 @@ class ArenaLayout(BlockLayout):
 
     def _crc(self, meta, off, n):
         return self.arena.crc32c(meta["offset"] + off, n)
+
+    def _read_lz4(self, meta, off, n):
+        return self.arena.lz4_compress(meta["offset"] + off, n)
+
+    def _write_lz4_at(self, meta, off, container):
+        return self.arena.lz4_decompress_into(meta["offset"] + off, container)
 
     def local_info(self, meta: dict) -> dict:
         info = {"kind": "arena", "tier": self.tier,

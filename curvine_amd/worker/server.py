@@ -27,6 +27,10 @@ from curvine_amd.worker.handlers import WorkerHandler
 
 log = logging.getLogger("curvine.worker")
 
+# raw bytes per segment of the LZ4 replication push (the device compressor
+# takes at most 16 MiB per call; 8 MiB keeps its scratch at ~16 MiB)
+REPLICATION_LZ4_SEGMENT = 8 << 20
+
 
 class WorkerService(HandlerService):
     def __init__(self, worker: "Worker"):
@@ -40,6 +44,9 @@ class Worker:
     def __init__(self, conf: ClusterConf, worker_id: int | None = None,
                  device_id: int = -1):
         self.conf = conf
+        conf.worker.validate()
+        from curvine_amd.metrics import Counters, WORKER_COUNTERS
+        self.counters = Counters(WORKER_COUNTERS)
         self.worker_id = worker_id if worker_id is not None \
             else random.getrandbits(31)
         self.device_id = device_id
@@ -171,7 +178,68 @@ class Worker:
             log.exception("command %s failed: %s", cmd.get("cmd"), e)
 
     # ---------------- replication (worker side) ----------------
+    async def _replicate_lz4(self, cmd: dict) -> None:
+        """LZ4 replication push: the block is walked in
+        REPLICATION_LZ4_SEGMENT raw segments, each compressed where it
+        lives (HIP kernel for HBM blocks, so only compressed bytes cross
+        D2H, the wire and the target's H2D); a segment that does not
+        shrink is sent raw.  The target verifies the block's stored CRC at
+        commit."""
+        from curvine_amd.client.block_client import BlockWriterLz4Remote
+        async with self._repl_sem:
+            bid = cmd["block_id"]
+            ok, error = True, ""
+            try:
+                loop = asyncio.get_event_loop()
+                reader = await loop.run_in_executor(None,
+                                                    self.store.open_reader, bid)
+                try:
+                    targets = [WorkerAddress.from_dict(t)
+                               for t in cmd.get("targets", [])]
+                    seg = REPLICATION_LZ4_SEGMENT
+                    for t in targets:
+                        w = BlockWriterLz4Remote(t, bid, reader.length,
+                                                 cmd.get("tier", ""))
+                        try:
+                            pos = 0
+                            while pos < reader.length:
+                                n = min(seg, reader.length - pos)
+                                data = await loop.run_in_executor(
+                                    None, reader.read_lz4, pos, n)
+                                codec = "cvlz"
+                                if len(data) >= n:   # incompressible
+                                    data = await loop.run_in_executor(
+                                        None, reader.read, pos, n)
+                                    codec = "raw"
+                                await w.write_segment(data, codec)
+                                self.counters.inc(
+                                    "replication_lz4_segments"
+                                    if codec == "cvlz"
+                                    else "replication_raw_segments")
+                                self.counters.inc("replication_raw_bytes", n)
+                                self.counters.inc("replication_wire_bytes",
+                                                  len(data))
+                                pos += n
+                            await w.commit(reader.length,
+                                           self.store.block_crc(bid))
+                        except BaseException:
+                            await w.abort()
+                            raise
+                finally:
+                    reader.close()
+            except Exception as e:  # noqa: BLE001
+                ok, error = False, str(e)
+                log.warning("replicate block %d failed: %s", bid, e)
+            try:
+                await self._master.rpc(RpcCode.ReportBlockReplicationResult, {
+                    "block_id": bid, "job_id": cmd.get("job_id"),
+                    "success": ok, "error": error})
+            except Exception:  # noqa: BLE001
+                pass
+
     async def _replicate(self, cmd: dict) -> None:
+        if self.conf.worker.replication_codec == "lz4":
+            return await self._replicate_lz4(cmd)
         from curvine_amd.client.block_client import (BlockWriterRemote,
                                                      _native_data_lib,
                                                      _raise_wire_error)

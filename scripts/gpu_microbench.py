@@ -26,8 +26,63 @@ def timeit(fn, n=5, warmup=2):
     return (time.perf_counter() - t0) / n
 
 
+def bench_lz4(a, rng, results):
+    mod = native.load()
+    # LZ4 device decompress: 512 MiB of ~3:1-compressible data
+    rep = np.frombuffer((b"curvine-amd lz4 block payload %06d " % 42) * 64,
+                        dtype=np.uint8)
+    block = np.tile(rep, (512 << 20) // len(rep) + 1)[:512 << 20].copy()
+    noise_idx = rng.choice(len(block), len(block) // 64, replace=False)
+    block[noise_idx] = rng.integers(0, 256, len(noise_idx), dtype=np.uint8)
+    comp = native.lz4_compress(block.tobytes())
+    results["lz4_ratio"] = round(len(block) / len(comp), 2)
+    dt = timeit(lambda: mod.arena_lz4_decompress(a.handle, 0, comp))
+    results["lz4_device_decompress_GBps"] = round(len(block) / dt / 1e9, 2)
+    back = np.zeros(1 << 20, dtype=np.uint8)
+    a.read(0, back, 0, 1 << 20)
+    assert back.tobytes() == block[:1 << 20].tobytes()
+    dt = timeit(lambda: native.lz4_decompress(comp))
+    results["lz4_host_decompress_GBps"] = round(len(block) / dt / 1e9, 2)
+
+    # LZ4 device compress: the first 16 MiB of that block (one call's
+    # limit), read where it lives in the arena, against the host codec —
+    # the only other way the product has to make a container
+    cn = 16 << 20
+    raw = block[:cn].tobytes()
+    a.write(0, raw, 0, cn)
+    dev_c = a.lz4_compress(0, cn)
+    assert native.lz4_decompress(dev_c) == raw
+    dt = timeit(lambda: a.lz4_compress(0, cn))
+    dev_gbps = cn / dt / 1e9
+    results["lz4_device_compress_GBps"] = round(dev_gbps, 2)
+    host_c = native.lz4_compress(raw)
+    dt = timeit(lambda: native.lz4_compress(raw))
+    host_gbps = cn / dt / 1e9
+    results["lz4_host_compress_GBps"] = round(host_gbps, 3)
+    results["lz4_device_vs_host_size"] = round(len(dev_c) / len(host_c), 4)
+    results["lz4_compress_raw_bytes"] = cn
+    results["lz4_device_container_bytes"] = len(dev_c)
+    results["lz4_host_container_bytes"] = len(host_c)
+    # does compressing before the host link pay?  57 GB/s = pinned D2H
+    link = 57.0
+    t_lz4 = cn / dev_gbps / 1e9 + len(dev_c) / link / 1e9
+    t_raw = cn / link / 1e9
+    results["lz4_device_faster_than_host"] = bool(dev_gbps > host_gbps)
+    results["lz4_compress_then_d2h_us"] = round(t_lz4 * 1e6, 1)
+    results["raw_d2h_us"] = round(t_raw * 1e6, 1)
+    results["lz4_compress_then_d2h_beats_raw_d2h"] = bool(t_lz4 < t_raw)
+
+
 def main():
     assert native.gpu_available(), "needs a GPU"
+    if "--lz4-only" in sys.argv[1:]:
+        a = native.Arena(0, (512 << 20) + (1 << 20), staging_bytes=16 << 20,
+                         staging_count=8)
+        results = {}
+        bench_lz4(a, np.random.default_rng(1), results)
+        print(json.dumps(results, indent=1))
+        a.close()
+        return
     GB = 1 << 30
     size = 4 * GB
     a = native.Arena(0, size + (1 << 20), staging_bytes=16 << 20,
@@ -98,21 +153,7 @@ def main():
     results["gather_dev_4096x256KiB_GBps"] = round(
         2 * n_s * s_sz / dt / 1e9, 2)   # rd+wr bytes
 
-    # LZ4 device decompress: 512 MiB of ~3:1-compressible data
-    rep = np.frombuffer((b"curvine-amd lz4 block payload %06d " % 42) * 64,
-                        dtype=np.uint8)
-    block = np.tile(rep, (512 << 20) // len(rep) + 1)[:512 << 20].copy()
-    noise_idx = rng.choice(len(block), len(block) // 64, replace=False)
-    block[noise_idx] = rng.integers(0, 256, len(noise_idx), dtype=np.uint8)
-    comp = native.lz4_compress(block.tobytes())
-    results["lz4_ratio"] = round(len(block) / len(comp), 2)
-    dt = timeit(lambda: mod.arena_lz4_decompress(a.handle, 0, comp))
-    results["lz4_device_decompress_GBps"] = round(len(block) / dt / 1e9, 2)
-    back = np.zeros(1 << 20, dtype=np.uint8)
-    a.read(0, back, 0, 1 << 20)
-    assert back.tobytes() == block[:1 << 20].tobytes()
-    dt = timeit(lambda: native.lz4_decompress(comp))
-    results["lz4_host_decompress_GBps"] = round(len(block) / dt / 1e9, 2)
+    bench_lz4(a, rng, results)
 
     print(json.dumps(results, indent=1))
     a.close()
