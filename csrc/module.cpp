@@ -141,6 +141,7 @@ static uint32_t crc32c_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
 // ---------------------------------------------------------------------------
 #include "kernels.hip"
 #include "lz4.hip"
+#include "tensor_cast.hip"
 
 // ---------------------------------------------------------------------------
 // GPU availability
@@ -871,6 +872,119 @@ static void arena_gather_ptr(
   HIP_CHECK(hipStreamSynchronize(a->kstream));
 }
 
+// ---- typed tensor load (tensor_cast.hip) ----
+//
+// Segments: (src_off, dst_ptr, rows, run, src_pitch, src_dtype, dst_dtype).
+// Every argument error is raised here, on the host, before any launch.
+
+static CastSeg cast_validate(uint64_t cap, uint64_t src_off, uint64_t dst_ptr,
+                             uint64_t rows, uint64_t run, uint64_t pitch,
+                             uint64_t sdt, uint64_t ddt) {
+  if (sdt >= DT_COUNT || ddt >= DT_COUNT)
+    throw std::invalid_argument("convert: unknown dtype code");
+  if (sdt != ddt && !cast_pair_converts((uint32_t)sdt, (uint32_t)ddt))
+    throw std::invalid_argument("convert: unsupported dtype pair");
+  uint64_t ss = cast_itemsize((uint32_t)sdt), ds = cast_itemsize((uint32_t)ddt);
+  uint64_t run_b, span, end, total, dst_b;
+  if (__builtin_mul_overflow(run, ss, &run_b) ||
+      __builtin_mul_overflow(rows, run, &total) ||
+      __builtin_mul_overflow(total, ds, &dst_b) ||
+      __builtin_add_overflow(dst_ptr, dst_b, &end))
+    throw std::invalid_argument("convert: segment size overflows");
+  if (total) {
+    // last byte touched: src_off + (rows-1)*pitch + run*ss, overflow-checked
+    if (__builtin_mul_overflow(rows - 1, pitch, &span) ||
+        __builtin_add_overflow(span, run_b, &span) ||
+        __builtin_add_overflow(src_off, span, &end))
+      throw std::invalid_argument("convert: segment range overflows");
+    if (end > cap) throw std::invalid_argument("convert: arena range out of bounds");
+    if (dst_ptr == 0 || dst_ptr % ds)
+      throw std::invalid_argument("convert: dst_ptr null or misaligned");
+  }
+  CastSeg g;
+  g.src_off = src_off; g.dst_ptr = dst_ptr; g.rows = rows; g.run = run;
+  g.src_pitch = pitch; g.src_dt = (uint32_t)sdt; g.dst_dt = (uint32_t)ddt;
+  if (sdt == ddt) {            // raw copy at any itemsize: flatten to bytes
+    g.run = run_b;
+    g.src_dt = g.dst_dt = DT_U8;
+  }
+  return g;
+}
+
+typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                   uint64_t> CastSegTuple;
+
+static void arena_convert_ptr(int h, std::vector<CastSegTuple> segs_in) {
+  Arena* a = get_arena(h);
+  std::vector<CastSeg> segs;
+  segs.reserve(segs_in.size());
+  for (auto& t : segs_in) {
+    CastSeg g = cast_validate(a->cap, std::get<0>(t), std::get<1>(t),
+                              std::get<2>(t), std::get<3>(t), std::get<4>(t),
+                              std::get<5>(t), std::get<6>(t));
+    if (g.rows * g.run) segs.push_back(g);
+  }
+  if (segs.empty()) return;
+  py::gil_scoped_release rel;
+  if (!a->is_dev()) {
+    for (auto& g : segs) convert_segment_host((const uint8_t*)a->base, g);
+    return;
+  }
+  std::vector<uint32_t> tile_seg;
+  std::vector<uint64_t> tile_off;
+  for (size_t i = 0; i < segs.size(); ++i) {
+    uint64_t total = segs[i].rows * segs[i].run;
+    uint64_t step = cast_tile_elems(segs[i].src_dt, segs[i].dst_dt);
+    for (uint64_t t = 0; t < total; t += step) {
+      tile_seg.push_back((uint32_t)i);
+      tile_off.push_back(t);
+    }
+  }
+  if (tile_seg.size() > 0xFFFFFFFFull)
+    throw std::invalid_argument("convert: too many tiles in one call");
+  std::lock_guard<std::mutex> g(a->mu);
+  HIP_CHECK(hipSetDevice(a->device));
+  size_t seg_b = segs.size() * sizeof(CastSeg);
+  size_t off_b = tile_off.size() * sizeof(uint64_t);
+  size_t idx_b = tile_seg.size() * sizeof(uint32_t);
+  ensure_scratch(a, seg_b + off_b + idx_b + 64);
+  // 8-byte fields first so every table keeps its natural alignment
+  CastSeg* d_seg = (CastSeg*)a->scratch;
+  uint64_t* d_to = (uint64_t*)((uint8_t*)a->scratch + seg_b);
+  uint32_t* d_ts = (uint32_t*)((uint8_t*)a->scratch + seg_b + off_b);
+  HIP_CHECK(hipMemcpyAsync(d_seg, segs.data(), seg_b, hipMemcpyHostToDevice,
+                           a->kstream));
+  HIP_CHECK(hipMemcpyAsync(d_to, tile_off.data(), off_b, hipMemcpyHostToDevice,
+                           a->kstream));
+  HIP_CHECK(hipMemcpyAsync(d_ts, tile_seg.data(), idx_b, hipMemcpyHostToDevice,
+                           a->kstream));
+  int grid = (int)std::min<size_t>(tile_seg.size(), 8192);
+  (void)hipGetLastError();   // clear stale per-thread state
+  hipLaunchKernelGGL(convert_segments_kernel, dim3(grid), dim3(WG), 0,
+                     a->kstream, (const uint8_t*)a->base, d_seg, d_ts, d_to,
+                     (uint32_t)tile_seg.size());
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(a->kstream));
+}
+
+// host conversion of `n` packed elements (the slow path of the typed
+// reader: file-tier extents and elements straddling a block boundary go
+// through the same scalar routines as the kernel)
+static py::bytes convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
+                              uint64_t n) {
+  py::buffer_info bi = src.request();
+  uint64_t ds = ddt < DT_COUNT ? cast_itemsize((uint32_t)ddt) : 1;
+  uint64_t out_b;
+  if (__builtin_mul_overflow(n, ds, &out_b) || out_b > (1ull << 40))
+    throw std::invalid_argument("convert: segment size overflows");
+  // 8-byte words: aligned for every destination itemsize
+  std::vector<uint64_t> out(out_b / 8 + 1);
+  CastSeg g = cast_validate((uint64_t)bi.size * bi.itemsize, 0,
+                            (uint64_t)(uintptr_t)out.data(), 1, n, 0, sdt, ddt);
+  if (g.rows * g.run) convert_segment_host((const uint8_t*)bi.ptr, g);
+  return py::bytes((const char*)out.data(), out_b);
+}
+
 static uintptr_t arena_base_ptr(int h) {
   return (uintptr_t)get_arena(h)->base;
 }
@@ -1430,6 +1544,8 @@ PYBIND11_MODULE(_native, m) {
   m.def("arena_crc32c", &arena_crc32c);
   m.def("arena_gather", &arena_gather);
   m.def("arena_gather_ptr", &arena_gather_ptr);
+  m.def("arena_convert_ptr", &arena_convert_ptr);
+  m.def("convert_host", &convert_host);
   m.def("arena_base_ptr", &arena_base_ptr);
   m.def("arena_read_batch", &arena_read_batch);
   m.def("reader_register", &reader_register);
@@ -1500,5 +1616,6 @@ PYBIND11_MODULE(_native, m) {
   m.def("crc32c", &crc32c_buf, py::arg("buf"), py::arg("init") = 0);
   m.def("crc32c_combine", &crc32c_combine);
   m.attr("CRC_SUB") = CRC_SUB;
+  m.attr("CAST_TILE") = CAST_TILE;
   m.attr("__hip_arch__") = "gfx950";
 }

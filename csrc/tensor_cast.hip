@@ -1,0 +1,329 @@
+// Typed tensor load for curvine_amd: arena bytes -> dtype-converted,
+// optionally strided, dense destination (safetensors weights living in the
+// HBM cache land in torch parameters in one pass).
+//
+// One segment = `rows` runs of `run` contiguous source elements, the runs
+// `src_pitch` bytes apart in the arena, written densely at `dst_ptr`.  The
+// source may sit at ANY byte alignment (the safetensors data section starts
+// wherever the JSON header ends); the destination is aligned to its own
+// itemsize (torch allocations) but run boundaries inside it are not.
+//
+// Numerics: integer bit manipulation only, shared by the kernel and the
+// host loop (`__host__ __device__`), bitwise equal to torch's CPU `.to()`:
+// round-to-nearest-even downcasts, subnormals kept in both directions,
+// overflow to inf, every narrow source widened exactly to f32 first so
+// bf16<->f16 rounds once.
+//
+// Access pattern (memory-bound, no LDS): a unit is the element group whose
+// wider side is 16 B, one unit per lane per pass, so both the load and the
+// store instruction of a wave are contiguous.  Source tiers: vector load
+// when the run start allows it, aligned dwords, aligned dwords + byte
+// shift for odd offsets, byte loads for heads/tails/short runs.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstring>
+
+#ifndef WG
+#define WG 256
+#endif
+
+// dtype codes (mirrored by curvine_amd.native.DTYPES)
+enum CastDt : uint32_t {
+  DT_F32 = 0, DT_F16 = 1, DT_BF16 = 2, DT_F8_E4M3 = 3, DT_F8_E5M2 = 4,
+  DT_F64 = 5, DT_I64 = 6, DT_I32 = 7, DT_I16 = 8, DT_I8 = 9, DT_U8 = 10,
+  DT_BOOL = 11, DT_U16 = 12, DT_U32 = 13, DT_U64 = 14, DT_COUNT = 15
+};
+
+__host__ __device__ inline uint32_t cast_itemsize(uint32_t dt) {
+  switch (dt) {
+    case DT_F64: case DT_I64: case DT_U64: return 8;
+    case DT_F32: case DT_I32: case DT_U32: return 4;
+    case DT_F16: case DT_BF16: case DT_I16: case DT_U16: return 2;
+    default: return 1;
+  }
+}
+
+// a converting pair: narrow/wide float source, F32/F16/BF16 destination
+__host__ __device__ inline bool cast_pair_converts(uint32_t s, uint32_t d) {
+  return s != d && s <= DT_F8_E5M2 && d <= DT_BF16;
+}
+
+// ---------------------------------------------------------------------------
+// Scalar conversions on raw bit patterns (the ONE definition; host + device)
+// ---------------------------------------------------------------------------
+
+__host__ __device__ inline uint32_t cvt_f16_to_f32(uint32_t h) {
+  uint32_t sign = (h & 0x8000u) << 16;
+  uint32_t e = (h >> 10) & 31u, m = h & 0x3FFu;
+  if (e == 31u) return sign | 0x7F800000u | (m << 13);
+  if (e == 0u) {
+    if (m == 0u) return sign;
+    // subnormal m * 2^-24: top set bit p -> 2^(p-24) * 1.x
+    uint32_t p = 31u - (uint32_t)__builtin_clz(m);
+    return sign | ((p + 103u) << 23) | ((m << (23u - p)) & 0x7FFFFFu);
+  }
+  return sign | ((e + 112u) << 23) | (m << 13);
+}
+
+__host__ __device__ inline uint32_t cvt_f8e4m3_to_f32(uint32_t b) {
+  uint32_t sign = (b & 0x80u) << 24;
+  uint32_t e = (b >> 3) & 15u, m = b & 7u;
+  if (e == 15u && m == 7u) return sign | 0x7FC00000u;   // the only NaN, no inf
+  if (e == 0u) {
+    if (m == 0u) return sign;
+    uint32_t p = 31u - (uint32_t)__builtin_clz(m);      // m * 2^-9
+    return sign | ((p + 118u) << 23) | ((m << (23u - p)) & 0x7FFFFFu);
+  }
+  return sign | ((e + 120u) << 23) | (m << 20);
+}
+
+// widen any supported float source to exact f32 bits
+__host__ __device__ inline uint32_t cvt_to_f32(uint32_t bits, uint32_t sdt) {
+  switch (sdt) {
+    case DT_F16: return cvt_f16_to_f32(bits);
+    case DT_BF16: return bits << 16;
+    case DT_F8_E4M3: return cvt_f8e4m3_to_f32(bits);
+    case DT_F8_E5M2: return cvt_f16_to_f32(bits << 8);  // e5m2 = top byte of f16
+    default: return bits;
+  }
+}
+
+__host__ __device__ inline uint32_t cvt_f32_to_bf16(uint32_t u) {
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return ((u >> 16) & 0x8000u) | 0x7FC0u;
+  return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;   // RNE; inf/subnormal safe
+}
+
+__host__ __device__ inline uint32_t cvt_f32_to_f16(uint32_t u) {
+  uint32_t sign = (u >> 16) & 0x8000u;
+  uint32_t a = u & 0x7FFFFFFFu;
+  if (a >= 0x7F800000u) return sign | (a > 0x7F800000u ? 0x7E00u : 0x7C00u);
+  if (a >= 0x47800000u) return sign | 0x7C00u;          // >= 65536
+  if (a < 0x38800000u) {                                // < 2^-14: subnormal out
+    if (a <= 0x33000000u) return sign;                  // <= 2^-25 (tie -> even 0)
+    uint32_t e = a >> 23;                               // 102..112
+    uint32_t m = (a & 0x7FFFFFu) | 0x800000u;
+    uint32_t sh = 126u - e;                             // 14..24
+    uint32_t r = m >> sh, rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+    if (rem > half || (rem == half && (r & 1u))) r++;   // may carry to 0x0400
+    return sign | r;
+  }
+  uint32_t r = a - 0x38000000u;                         // rebias 127 -> 15
+  r += 0xFFFu + ((r >> 13) & 1u);                       // RNE; 65520 -> inf
+  return sign | (r >> 13);
+}
+
+__host__ __device__ inline uint32_t cvt_from_f32(uint32_t f, uint32_t ddt) {
+  switch (ddt) {
+    case DT_F16: return cvt_f32_to_f16(f);
+    case DT_BF16: return cvt_f32_to_bf16(f);
+    default: return f;
+  }
+}
+
+// one element, byte loads, store at the destination itemsize
+__host__ __device__ inline void cast_one(const uint8_t* s, uint8_t* d,
+                                         uint32_t sdt, uint32_t ddt) {
+  uint32_t ss = cast_itemsize(sdt);
+  uint32_t bits = 0;
+  for (uint32_t i = 0; i < ss; ++i) bits |= (uint32_t)s[i] << (8u * i);
+  uint32_t out = cvt_from_f32(cvt_to_f32(bits, sdt), ddt);
+  if (ddt == DT_F32) *reinterpret_cast<uint32_t*>(d) = out;
+  else *reinterpret_cast<uint16_t*>(d) = (uint16_t)out;
+}
+
+// ---------------------------------------------------------------------------
+// Kernel
+// ---------------------------------------------------------------------------
+
+struct CastSeg {
+  uint64_t src_off;     // bytes into the arena, any alignment
+  uint64_t dst_ptr;     // absolute address of dense element 0
+  uint64_t rows, run;   // rows runs of run elements
+  uint64_t src_pitch;   // bytes between run starts in the source
+  uint32_t src_dt, dst_dt;
+};
+
+// dense destination elements per workgroup tile; same-dtype copies are
+// flattened to bytes by the host and tile at 64 KiB like copy_extents_kernel
+#define CAST_TILE 16384
+__host__ __device__ inline uint64_t cast_tile_elems(uint32_t sdt, uint32_t ddt) {
+  return sdt == ddt ? 4u * CAST_TILE : CAST_TILE;
+}
+// runs shorter than this are handled element-wise with div/mod
+#define CAST_SHORT_RUN 64
+
+// load W dwords of source for one unit. mode 0: natural vector alignment,
+// 1: 4-byte aligned, 2: unaligned (aligned dwords + byte funnel shift; reads
+// up to 3 bytes before p and up to 4 bytes past the unit, which the caller
+// guarantees to lie inside the run's source bytes or the arena's first word)
+template <int W>
+__device__ __forceinline__ void cast_load_words(const uint8_t* p, int mode,
+                                                uint32_t (&w)[W]) {
+  if (mode == 0) {
+    if constexpr (W == 4) {
+      uint4 v = *reinterpret_cast<const uint4*>(p);
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    } else if constexpr (W == 2) {
+      uint2 v = *reinterpret_cast<const uint2*>(p);
+      w[0] = v.x; w[1] = v.y;
+    } else {
+      w[0] = *reinterpret_cast<const uint32_t*>(p);
+    }
+  } else if (mode == 1) {
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(p);
+#pragma unroll
+    for (int i = 0; i < W; ++i) w[i] = q[i];
+  } else {
+    uint32_t sh = ((uint32_t)(uintptr_t)p & 3u) * 8u;   // 8, 16 or 24
+    const uint32_t* q = reinterpret_cast<const uint32_t*>(
+        (uintptr_t)p & ~(uintptr_t)3);
+    uint32_t t[W + 1];
+#pragma unroll
+    for (int i = 0; i <= W; ++i) t[i] = q[i];
+#pragma unroll
+    for (int i = 0; i < W; ++i) w[i] = (t[i] >> sh) | (t[i + 1] << (32u - sh));
+  }
+}
+
+template <int OW>
+__device__ __forceinline__ void cast_store_words(uint8_t* p,
+                                                 const uint32_t (&o)[OW]) {
+  if constexpr (OW == 4) {
+    *reinterpret_cast<uint4*>(p) = make_uint4(o[0], o[1], o[2], o[3]);
+  } else {
+    *reinterpret_cast<uint2*>(p) = make_uint2(o[0], o[1]);
+  }
+}
+
+template <uint32_t SDT, int SS>
+__device__ __forceinline__ uint32_t cast_extract(const uint32_t* w, int k) {
+  if constexpr (SS == 4) return w[k];
+  else if constexpr (SS == 2) return (w[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
+  else return (w[k >> 2] >> ((k & 3) * 8)) & 0xFFu;
+}
+
+// one contiguous run of n elements, all WG threads cooperating.
+// SDT == DDT == DT_U8 is the raw byte copy.
+template <uint32_t SDT, uint32_t DDT>
+__device__ __forceinline__ void cast_run(const uint8_t* s, uint8_t* d,
+                                         uint64_t n) {
+  constexpr bool COPY = (SDT == DDT);
+  constexpr int SS = COPY ? 1 : (SDT == DT_F32 ? 4 : (SDT <= DT_BF16 ? 2 : 1));
+  constexpr int DS = COPY ? 1 : (DDT == DT_F32 ? 4 : 2);
+  constexpr int K = 16 / (SS > DS ? SS : DS);   // elements per unit
+  constexpr int W = K * SS / 4;                 // source dwords per unit
+  constexpr int OW = K * DS / 4;                // destination dwords per unit
+
+  // head: up to the first destination address aligned to the unit store
+  uint64_t hd = ((0 - (uintptr_t)d) & (uintptr_t)(K * DS - 1)) / DS;
+  if (hd > n) hd = n;
+  uint64_t nb = (n - hd) / K;
+  const uint8_t* sb = s + hd * SS;
+  int mode = ((uintptr_t)sb & (W * 4 - 1)) == 0 ? 0
+             : (((uintptr_t)sb & 3) == 0 ? 1 : 2);
+  // the shifted loads over-read past their unit: keep the last unit out of
+  // the body so the over-read stays inside this run's own source bytes
+  if (mode == 2 && nb > 0) nb--;
+  uint64_t tail0 = hd + nb * K;
+
+  for (uint64_t u = threadIdx.x; u < nb; u += WG) {
+    uint32_t w[W], o[OW];
+    cast_load_words<W>(sb + u * (K * SS), mode, w);
+    if constexpr (COPY) {
+#pragma unroll
+      for (int i = 0; i < OW; ++i) o[i] = w[i];
+    } else {
+#pragma unroll
+      for (int k = 0; k < K; ++k) {
+        uint32_t r = cvt_from_f32(
+            cvt_to_f32(cast_extract<SDT, SS>(w, k), SDT), DDT);
+        if constexpr (DS == 4) o[k] = r;
+        else if ((k & 1) == 0) o[k >> 1] = r;
+        else o[k >> 1] |= r << 16;
+      }
+    }
+    cast_store_words<OW>(d + (hd + u * K) * DS, o);
+  }
+  // head + tail: at most 3*K elements, byte loads, element stores
+  uint64_t edge = hd + (n - tail0);
+  for (uint64_t i = threadIdx.x; i < edge; i += WG) {
+    uint64_t e = i < hd ? i : tail0 + (i - hd);
+    if constexpr (COPY) d[e] = s[e];
+    else cast_one(s + e * SS, d + e * DS, SDT, DDT);
+  }
+}
+
+template <uint32_t SDT, uint32_t DDT>
+__device__ __forceinline__ void cast_tile(const uint8_t* base,
+                                          const CastSeg& g, uint64_t t0,
+                                          uint64_t t1) {
+  constexpr bool COPY = (SDT == DDT);
+  constexpr uint32_t SS = COPY ? 1 : (SDT == DT_F32 ? 4 : (SDT <= DT_BF16 ? 2 : 1));
+  constexpr uint32_t DS = COPY ? 1 : (DDT == DT_F32 ? 4 : 2);
+  const uint8_t* src = base + g.src_off;
+  uint8_t* dst = reinterpret_cast<uint8_t*>(g.dst_ptr);
+  if (g.run >= CAST_SHORT_RUN) {
+    uint64_t e = t0;
+    while (e < t1) {                       // workgroup-uniform loop
+      uint64_t r = e / g.run, c = e - r * g.run;
+      uint64_t len = min(g.run - c, t1 - e);
+      cast_run<SDT, DDT>(src + r * g.src_pitch + c * SS, dst + e * DS, len);
+      e += len;
+    }
+  } else {
+    // many short runs: element-wise, one div per element
+    for (uint64_t e = t0 + threadIdx.x; e < t1; e += WG) {
+      uint64_t r = e / g.run, c = e - r * g.run;
+      const uint8_t* sp = src + r * g.src_pitch + c * SS;
+      if constexpr (COPY) dst[e] = *sp;
+      else cast_one(sp, dst + e * DS, SDT, DDT);
+    }
+  }
+}
+
+// Tile table as in copy_extents_kernel: tile -> segment, tile -> first dense
+// element; grid-stride over tiles so one huge embedding and 300
+// norm vectors in the same call spread evenly over the CUs.
+extern "C" __global__ __launch_bounds__(WG) void convert_segments_kernel(
+    const uint8_t* __restrict__ base, const CastSeg* __restrict__ segs,
+    const uint32_t* __restrict__ tile_seg, const uint64_t* __restrict__ tile_off,
+    uint32_t n_tiles) {
+  for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    CastSeg g = segs[tile_seg[tile]];
+    uint64_t t0 = tile_off[tile];
+    uint64_t t1 = min(t0 + cast_tile_elems(g.src_dt, g.dst_dt),
+                      g.rows * g.run);
+#define CAST_CASE(S, D) \
+    case (S) * 16u + (D): cast_tile<S, D>(base, g, t0, t1); break;
+    switch (g.src_dt * 16u + g.dst_dt) {
+      CAST_CASE(DT_U8, DT_U8)
+      CAST_CASE(DT_F32, DT_F16) CAST_CASE(DT_F32, DT_BF16)
+      CAST_CASE(DT_F16, DT_F32) CAST_CASE(DT_F16, DT_BF16)
+      CAST_CASE(DT_BF16, DT_F32) CAST_CASE(DT_BF16, DT_F16)
+      CAST_CASE(DT_F8_E4M3, DT_F32) CAST_CASE(DT_F8_E4M3, DT_F16)
+      CAST_CASE(DT_F8_E4M3, DT_BF16)
+      CAST_CASE(DT_F8_E5M2, DT_F32) CAST_CASE(DT_F8_E5M2, DT_F16)
+      CAST_CASE(DT_F8_E5M2, DT_BF16)
+      default: break;   // host rejects every other pair before launch
+    }
+#undef CAST_CASE
+  }
+}
+
+// host arena: the same segments, the same scalar routines, plain loops
+static void convert_segment_host(const uint8_t* base, const CastSeg& g) {
+  uint32_t ss = cast_itemsize(g.src_dt), ds = cast_itemsize(g.dst_dt);
+  uint8_t* dst = reinterpret_cast<uint8_t*>(g.dst_ptr);
+  for (uint64_t r = 0; r < g.rows; ++r) {
+    const uint8_t* s = base + g.src_off + r * g.src_pitch;
+    uint8_t* d = dst + r * g.run * ds;
+    if (g.src_dt == g.dst_dt) {
+      std::memcpy(d, s, g.run * ss);
+      continue;
+    }
+    for (uint64_t c = 0; c < g.run; ++c)
+      cast_one(s + c * ss, d + c * ds, g.src_dt, g.dst_dt);
+  }
+}

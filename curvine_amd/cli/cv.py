@@ -333,6 +333,19 @@ def cmd_bench(fs, args):
         "write_MBps": round(wbps / 1e6, 1), "read_MBps": round(rbps / 1e6, 1)}))
 
 
+def cmd_tensors(fs, args):
+    """List the tensors of a cached safetensors file (header only)."""
+    from curvine_amd.sdk.safetensors_io import read_header
+    infos, _meta, start, _length = read_header(fs, args.path)
+    total = 0
+    for name, ti in infos.items():
+        b, e = ti.data_offsets
+        shape = "[" + ",".join(str(d) for d in ti.shape) + "]"
+        print(f"{name}\t{ti.dtype}\t{shape}\t{start + b}..{start + e}")
+        total += e - b
+    print(f"total: {len(infos)} tensors, {fmt_bytes(total)} ({total} bytes)")
+
+
 def cmd_validate(_fs, args):
     """Offline config validation (cli/validate_run.rs analog): parse the
     TOML, check tier specs / ports / peer addresses, print a summary."""
@@ -403,6 +416,7 @@ def build_parser() -> argparse.ArgumentParser:
     add("get", cmd_get, A("src"), A("dst"))
     add("stat", cmd_stat, A("path"))
     add("blocks", cmd_blocks, A("path"))
+    add("tensors", cmd_tensors, A("path"))
     add("du", cmd_du, A("path"))
     add("count", cmd_count, A("path"))
     add("df", cmd_df)

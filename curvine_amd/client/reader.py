@@ -259,6 +259,115 @@ class SyncLocalReader:
         for off, want, doff in slow:
             self.pread_into_ptr(off, dst_ptr + doff, want)
 
+    # ---------------- typed (dtype-converting) reads ----------------
+    def resolve_convert(self, requests, dst_on_device: bool):
+        """Typed analog of resolve_gather.  Each request is (file_off,
+        rows, run, src_pitch, src_dtype, dst_dtype, dst_ptr) with dtype
+        NAMES from native.DTYPES: `rows` runs of `run` elements,
+        `src_pitch` bytes apart in the file, land densely at dst_ptr as
+        dst_dtype.  Returns (groups, slow): groups = [(arena, segments)]
+        ready for Arena.convert_ptr, slow = [(file_off, n_elems,
+        src_dtype, dst_dtype, dst_ptr)] contiguous extents for the
+        pread + host-convert path (file tier, cross-side arenas, and the
+        single element that can straddle a block boundary when the data
+        section starts at an odd offset)."""
+        import bisect
+
+        from curvine_amd.native import DTYPE_ITEMSIZE, DTYPES
+        groups: dict[int, tuple[object, list]] = {}
+        slow: list[tuple[int, int, str, str, int]] = []
+        blocks = self.fb.blocks
+
+        def block_at(pos):
+            idx = bisect.bisect_right(self._offs, pos) - 1
+            if idx < 0 or idx >= len(self._readers):
+                return None
+            lb = blocks[idx]
+            if pos >= lb.offset + lb.block.length:
+                return None
+            return idx
+
+        for off, rows, run, pitch, sdt, ddt, dptr in requests:
+            if rows <= 0 or run <= 0:
+                continue
+            ss, ds = DTYPE_ITEMSIZE[sdt], DTYPE_ITEMSIZE[ddt]
+            sc, dc = DTYPES[sdt], DTYPES[ddt]
+            run_b = run * ss
+
+            def emit(idx, pos, n_rows, n_run, dst):
+                """n_rows runs of n_run elements, all inside block idx."""
+                r = self._readers[idx]
+                arena = getattr(r.layout, "arena", None)
+                same_side = r.meta.get("kind") == "arena" and \
+                    arena is not None and \
+                    ((arena.device >= 0) == bool(dst_on_device))
+                if same_side:
+                    _, segs = groups.setdefault(arena.handle, (arena, []))
+                    segs.append((r.meta["offset"] + pos - blocks[idx].offset,
+                                 dst, n_rows, n_run, pitch, sc, dc))
+                else:
+                    for k in range(n_rows):
+                        slow.append((pos + k * pitch, n_run, sdt, ddt,
+                                     dst + k * n_run * ds))
+
+            r_i = 0
+            while r_i < rows:
+                pos = off + r_i * pitch
+                dst = dptr + r_i * run * ds
+                idx = block_at(pos)
+                if idx is not None:
+                    end = blocks[idx].offset + blocks[idx].block.length
+                    if pos + run_b <= end:
+                        # every following run that also ends inside
+                        cnt = rows - r_i
+                        if pitch > 0:
+                            cnt = min(cnt, (end - run_b - pos) // pitch + 1)
+                        emit(idx, pos, cnt, run, dst)
+                        r_i += cnt
+                        continue
+                # a run cut by a block boundary (or a hole): rows=1 pieces
+                # split on whole elements
+                e = 0
+                while e < run:
+                    p = pos + e * ss
+                    idx = block_at(p)
+                    if idx is None:       # hole: pread synthesizes zeros
+                        slow.append((p, run - e, sdt, ddt, dst + e * ds))
+                        break
+                    avail = blocks[idx].offset + blocks[idx].block.length - p
+                    k = min(run - e, avail // ss)
+                    if k == 0:            # element straddles two blocks
+                        slow.append((p, 1, sdt, ddt, dst + e * ds))
+                        e += 1
+                        continue
+                    emit(idx, p, 1, k, dst + e * ds)
+                    e += k
+                r_i += 1
+        return list(groups.values()), slow
+
+    def exec_convert(self, groups, slow, dst_on_device: bool) -> None:
+        """Run a resolve_convert plan: one Arena.convert_ptr per arena,
+        then the slow list through pread -> host convert (the kernel's own
+        scalar routines) -> H2D copy or memcpy."""
+        import ctypes
+
+        from curvine_amd import native
+        for arena, segs in groups:
+            arena.convert_ptr(segs)
+        for off, n, sdt, ddt, dptr in slow:
+            raw = self.pread(off, n * native.DTYPE_ITEMSIZE[sdt])
+            if len(raw) != n * native.DTYPE_ITEMSIZE[sdt]:
+                raise err.OutOfRange(
+                    f"typed read at {off}: short read ({len(raw)} bytes)")
+            out = native.convert_host(raw, native.DTYPES[sdt],
+                                      native.DTYPES[ddt], n)
+            if dst_on_device:
+                buf = (ctypes.c_char * len(out)).from_buffer_copy(out)
+                native.load().memcpy_h2d(dptr, ctypes.addressof(buf),
+                                         len(out))
+            else:
+                ctypes.memmove(dptr, out, len(out))
+
     def verify(self) -> list[int]:
         """Recompute every resident block's CRC32C (HBM: device kernel)
         against the worker's publish-time value; returns block ids that

@@ -25,6 +25,7 @@ _SRC4 = os.path.join(_REPO, "csrc", "fuse_loop.hip")
 _SRC5 = os.path.join(_REPO, "csrc", "meta_server.cpp")
 _SRC6 = os.path.join(_REPO, "csrc", "data_server.cpp")
 _SRC7 = os.path.join(_REPO, "csrc", "sdk_abi.cpp")
+_SRC8 = os.path.join(_REPO, "csrc", "tensor_cast.hip")
 _lock = threading.Lock()
 _mod = None
 
@@ -38,7 +39,8 @@ def build_native(force: bool = False) -> str:
                                         os.path.getmtime(_SRC4),
                                         os.path.getmtime(_SRC5),
                                         os.path.getmtime(_SRC6),
-                                        os.path.getmtime(_SRC7)):
+                                        os.path.getmtime(_SRC7),
+                                        os.path.getmtime(_SRC8)):
             return _SO
     import pybind11
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -147,6 +149,17 @@ class Arena:
         hop); host arena requires a host dst (memcpy)."""
         self._n.arena_gather_ptr(self.handle, triples, dst_ptr)
 
+    def convert_ptr(self, segments: list[tuple]) -> None:
+        """Typed load: each segment (src_off, dst_ptr, rows, run,
+        src_pitch, src_dtype, dst_dtype) moves `rows` runs of `run`
+        elements, `src_pitch` bytes apart in the arena, densely to
+        `dst_ptr`, converting src_dtype -> dst_dtype (codes from DTYPES).
+        Device arena + device destinations = one convert_segments_kernel
+        launch for the whole list; host arena + host destinations = the
+        same scalar routines in C++.  Bad ranges, unknown codes and
+        unsupported pairs raise ValueError before anything runs."""
+        self._n.arena_convert_ptr(self.handle, segments)
+
     def lz4_compress(self, off: int, n: int) -> bytes:
         """Compress arena bytes [off, off+n) into a CVLZ container (HIP
         kernel on device arenas: only compressed bytes cross D2H; host
@@ -213,6 +226,28 @@ class PinnedBuffer:
             self.close()
         except Exception:
             pass
+
+
+# dtype name (safetensors spelling) -> code understood by convert_ptr
+DTYPES = {"F32": 0, "F16": 1, "BF16": 2, "F8_E4M3": 3, "F8_E5M2": 4,
+          "F64": 5, "I64": 6, "I32": 7, "I16": 8, "I8": 9, "U8": 10,
+          "BOOL": 11, "U16": 12, "U32": 13, "U64": 14}
+DTYPE_ITEMSIZE = {"F32": 4, "F16": 2, "BF16": 2, "F8_E4M3": 1, "F8_E5M2": 1,
+                  "F64": 8, "I64": 8, "I32": 4, "I16": 2, "I8": 1, "U8": 1,
+                  "BOOL": 1, "U16": 2, "U32": 4, "U64": 8}
+# floating sources the kernel converts, and the targets it converts to
+CONVERT_SOURCES = ("F32", "F16", "BF16", "F8_E4M3", "F8_E5M2")
+CONVERT_TARGETS = ("F32", "F16", "BF16")
+
+
+def convert_supported(src: str, dst: str) -> bool:
+    return src == dst or (src in CONVERT_SOURCES and dst in CONVERT_TARGETS)
+
+
+def convert_host(buf, src_dtype: int, dst_dtype: int, n: int) -> bytes:
+    """Convert `n` packed elements on the host with the kernel's own
+    scalar routines (bit-identical to the device path)."""
+    return load().convert_host(buf, src_dtype, dst_dtype, n)
 
 
 def crc32c(buf, init: int = 0) -> int:

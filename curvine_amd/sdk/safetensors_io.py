@@ -1,0 +1,332 @@
+"""Safetensors checkpoints in the cache -> typed torch tensors.
+
+The model-distribution path (BASELINE: "Llama-3-70B shards S3->HBM"):
+a `.safetensors` file whose blocks sit in the local worker's HBM arena is
+turned into parameters by ONE fused pass per arena — dtype cast
+(fp32/fp16/bf16 among each other, fp8 upcasts), tensor-parallel slicing
+and the unaligned data section are all handled inside
+`convert_segments_kernel` (csrc/tensor_cast.hip), with no temporary and no
+host hop.  MEM-tier files loaded onto `cpu` run the same segments through
+the same scalar routines in C++; anything else (file tier, cross-side)
+takes the slow, correct pread + host-convert path.
+
+The header parser is written here by hand: the `safetensors` package is
+not a dependency.
+"""
+from __future__ import annotations
+
+import json
+import struct
+from dataclasses import dataclass
+
+from curvine_amd import errors as err
+from curvine_amd.native import (CONVERT_SOURCES, DTYPE_ITEMSIZE,
+                                convert_supported)
+
+MAX_HEADER = 100 << 20
+
+
+@dataclass(frozen=True)
+class TensorInfo:
+    name: str
+    dtype: str                       # safetensors spelling, e.g. "BF16"
+    shape: tuple
+    data_offsets: tuple              # (begin, end) relative to the data section
+
+    @property
+    def numel(self) -> int:
+        n = 1
+        for d in self.shape:
+            n *= d
+        return n
+
+    @property
+    def nbytes(self) -> int:
+        return self.data_offsets[1] - self.data_offsets[0]
+
+
+def parse_header(head8: bytes, read, file_len: int):
+    """Parse a safetensors header.  `head8` = first 8 bytes, `read(off, n)`
+    fetches header bytes.  Returns (infos: dict name->TensorInfo in file
+    order, metadata: dict, data_start: int)."""
+    if len(head8) < 8:
+        raise err.InvalidArgument("safetensors: file shorter than 8 bytes")
+    (n,) = struct.unpack("<Q", head8)
+    if n > MAX_HEADER or 8 + n > file_len:
+        raise err.InvalidArgument(
+            f"safetensors: header length {n} exceeds the file or 100 MiB")
+    raw = read(8, n)
+    if len(raw) != n:
+        raise err.InvalidArgument("safetensors: short header read")
+
+    def pairs(items):
+        seen = {}
+        for k, v in items:
+            if k in seen:
+                raise err.InvalidArgument(
+                    f"safetensors: duplicate name {k!r}")
+            seen[k] = v
+        return seen
+
+    try:
+        doc = json.loads(bytes(raw).decode("utf-8"), object_pairs_hook=pairs)
+    except err.InvalidArgument:
+        raise
+    except (ValueError, UnicodeDecodeError) as e:
+        raise err.InvalidArgument(f"safetensors: bad header JSON: {e}")
+    if not isinstance(doc, dict):
+        raise err.InvalidArgument("safetensors: header is not a JSON object")
+    data_start = 8 + n
+    data_len = file_len - data_start
+    metadata = {}
+    infos: dict[str, TensorInfo] = {}
+    for name, ent in doc.items():
+        if name == "__metadata__":
+            if not isinstance(ent, dict):
+                raise err.InvalidArgument(
+                    "safetensors: '__metadata__' is not an object")
+            metadata = {str(k): str(v) for k, v in ent.items()}
+            continue
+        if not isinstance(ent, dict):
+            raise err.InvalidArgument(
+                f"safetensors: entry {name!r} is not an object")
+        dt = ent.get("dtype")
+        if dt not in DTYPE_ITEMSIZE:
+            raise err.InvalidArgument(
+                f"safetensors: tensor {name!r}: unknown dtype {dt!r}")
+        shape = ent.get("shape")
+        if not isinstance(shape, list) or any(
+                not isinstance(d, int) or isinstance(d, bool) for d in shape):
+            raise err.InvalidArgument(
+                f"safetensors: tensor {name!r}: bad shape {shape!r}")
+        if any(d < 0 for d in shape):
+            raise err.InvalidArgument(
+                f"safetensors: tensor {name!r}: negative dimension")
+        offs = ent.get("data_offsets")
+        if not isinstance(offs, list) or len(offs) != 2 or any(
+                not isinstance(o, int) or isinstance(o, bool) for o in offs):
+            raise err.InvalidArgument(
+                f"safetensors: tensor {name!r}: bad data_offsets {offs!r}")
+        begin, end = offs
+        if begin < 0 or begin > end or end > data_len:
+            raise err.InvalidArgument(
+                f"safetensors: tensor {name!r}: data_offsets {offs} out of "
+                f"range (data section is {data_len} bytes)")
+        numel = 1
+        for d in shape:
+            numel *= d
+        if end - begin != numel * DTYPE_ITEMSIZE[dt]:
+            raise err.InvalidArgument(
+                f"safetensors: tensor {name!r}: {end - begin} bytes for "
+                f"shape {shape} of {dt}")
+        infos[name] = TensorInfo(name, dt, tuple(shape), (begin, end))
+    return infos, metadata, data_start
+
+
+def read_header(sync_fs, path: str):
+    """Header-only parse through the async reader (no short-circuit
+    needed): (infos, metadata, data_start, file_len)."""
+    async def go():
+        r = await sync_fs.fs.open(path)
+        try:
+            head = await r.pread(0, 8)
+            n = struct.unpack("<Q", head)[0] if len(head) == 8 else 0
+            body = b""
+            if n <= MAX_HEADER and 8 + n <= r.length:
+                body = await r.pread(8, n)
+            return head, body, r.length
+        finally:
+            r.close()
+    head, body, length = sync_fs.call(go())
+    infos, meta, start = parse_header(head, lambda off, n: body, length)
+    return infos, meta, start, length
+
+
+def _torch_dtypes():
+    import torch
+    m = {"F32": torch.float32, "F16": torch.float16, "BF16": torch.bfloat16,
+         "F64": torch.float64, "I64": torch.int64, "I32": torch.int32,
+         "I16": torch.int16, "I8": torch.int8, "U8": torch.uint8,
+         "BOOL": torch.bool}
+    for name, attr in (("F8_E4M3", "float8_e4m3fn"),
+                       ("F8_E5M2", "float8_e5m2"), ("U16", "uint16"),
+                       ("U32", "uint32"), ("U64", "uint64")):
+        if hasattr(torch, attr):
+            m[name] = getattr(torch, attr)
+    return m
+
+
+_FLOATING = CONVERT_SOURCES + ("F64",)
+
+
+class CurvineSafetensors:
+    """One cached safetensors file.  Holds the file's SyncLocalReader open
+    (pinning its blocks) until close()."""
+
+    def __init__(self, sync_fs, path: str):
+        self.sync_fs = sync_fs
+        self.path = path
+        r = sync_fs.call(sync_fs.fs.open(path))
+        try:
+            self.reader = r.to_sync()
+        finally:
+            r.close()
+        try:
+            self._infos, self._meta, self.data_start = parse_header(
+                self.reader.pread(0, 8), self.reader.pread,
+                self.reader.length)
+        except Exception:
+            self.reader.close()
+            raise
+        self._t2s = None
+
+    # ---- header views ----
+    def keys(self) -> list[str]:
+        return list(self._infos)
+
+    def metadata(self) -> dict[str, str]:
+        return dict(self._meta)
+
+    def info(self, name: str) -> TensorInfo:
+        try:
+            return self._infos[name]
+        except KeyError:
+            raise err.InvalidArgument(f"safetensors: no tensor {name!r}")
+
+    # ---- planning ----
+    def _dst_dtype_name(self, info: TensorInfo, dtype) -> str:
+        """Stored dtype unless `dtype` is given and the tensor is floating
+        (integer/bool tensors keep theirs, as module.to(dtype) does)."""
+        if dtype is None or info.dtype not in _FLOATING:
+            return info.dtype
+        if self._t2s is None:
+            self._t2s = {v: k for k, v in _torch_dtypes().items()}
+        dst = self._t2s.get(dtype)
+        if dst is None or not convert_supported(info.dtype, dst):
+            raise err.Unsupported(
+                f"safetensors: tensor {info.name!r}: cannot load {info.dtype}"
+                f" as {dtype}")
+        return dst
+
+    @staticmethod
+    def _slice(info: TensorInfo, shard):
+        """(out_shape, rows, run, src_pitch_elems, first_elem) of the
+        tensor or of its equal shard (dim, rank, world)."""
+        shape = info.shape
+        if shard is None:
+            return shape, 1, info.numel, info.numel, 0
+        dim, rank, world = shard
+        nd = len(shape)
+        if not -nd <= dim < nd:
+            raise err.InvalidArgument(
+                f"safetensors: tensor {info.name!r}: shard dim {dim} out of "
+                f"range for shape {shape}")
+        dim %= nd
+        if world <= 0 or not 0 <= rank < world:
+            raise err.InvalidArgument(
+                f"safetensors: tensor {info.name!r}: bad shard rank/world "
+                f"{rank}/{world}")
+        if shape[dim] % world:
+            raise err.InvalidArgument(
+                f"safetensors: tensor {info.name!r}: dimension {dim} of size "
+                f"{shape[dim]} is not divisible by world {world}")
+        outer = inner = 1
+        for d in shape[:dim]:
+            outer *= d
+        for d in shape[dim + 1:]:
+            inner *= d
+        part = shape[dim] // world
+        out_shape = shape[:dim] + (part,) + shape[dim + 1:]
+        return (out_shape, outer, part * inner, shape[dim] * inner,
+                rank * part * inner)
+
+    def _request(self, info: TensorInfo, dst_name: str, shard, dst_ptr: int):
+        _, rows, run, pitch_el, first = self._slice(info, shard)
+        isz = DTYPE_ITEMSIZE[info.dtype]
+        off = self.data_start + info.data_offsets[0] + first * isz
+        if rows > 1 and run == pitch_el:      # dim-0-like: one run
+            rows, run = 1, rows * run
+        return (off, rows, run, pitch_el * isz, info.dtype, dst_name, dst_ptr)
+
+    def _execute(self, requests, dev) -> None:
+        on_dev = dev.type != "cpu"
+        groups, slow = self.reader.resolve_convert(requests, on_dev)
+        if on_dev:
+            import torch
+            # the kernel runs on the arena's own stream; the caching
+            # allocator may hand out memory torch's stream still uses
+            torch.cuda.current_stream(dev).synchronize()
+        self.reader.exec_convert(groups, slow, on_dev)
+
+    # ---- loading ----
+    def load(self, device="cuda:0", dtype=None, names=None,
+             shard_plan=None) -> dict:
+        """All (or `names`) tensors in one batched pass: every destination
+        is allocated, every tensor resolved, then ONE convert call per
+        arena covers the whole file."""
+        import torch
+        dev = torch.device(device)
+        tmap = _torch_dtypes()
+        shard_plan = shard_plan or {}
+        out, requests = {}, []
+        for name in (self.keys() if names is None else names):
+            info = self.info(name)
+            dst_name = self._dst_dtype_name(info, dtype)
+            if dst_name not in tmap:
+                raise err.Unsupported(
+                    f"safetensors: tensor {name!r}: this torch has no {dst_name}")
+            shard = shard_plan.get(name)
+            shape = self._slice(info, shard)[0]
+            t = torch.empty(shape, dtype=tmap[dst_name], device=dev)
+            out[name] = t
+            if t.numel():
+                requests.append(
+                    self._request(info, dst_name, shard, t.data_ptr()))
+        self._execute(requests, dev)
+        return out
+
+    def get_tensor(self, name: str, device="cuda:0", dtype=None, shard=None):
+        plan = None if shard is None else {name: shard}
+        return self.load(device, dtype, [name], plan)[name]
+
+    def load_into(self, name: str, tensor, shard=None) -> None:
+        """Fill an existing tensor (a module parameter): destination dtype
+        and device come from `tensor`."""
+        info = self.info(name)
+        shape = self._slice(info, shard)[0]
+        if tuple(tensor.shape) != tuple(shape):
+            raise err.InvalidArgument(
+                f"safetensors: tensor {name!r}: destination shape "
+                f"{tuple(tensor.shape)} != {tuple(shape)}")
+        if not tensor.is_contiguous():
+            raise err.InvalidArgument(
+                f"safetensors: tensor {name!r}: destination is not contiguous")
+        if tensor.device.type not in ("cpu", "cuda"):
+            raise err.InvalidArgument(
+                f"safetensors: tensor {name!r}: unsupported destination "
+                f"device {tensor.device}")
+        t2s = {v: k for k, v in _torch_dtypes().items()}
+        dst_name = t2s.get(tensor.dtype)
+        if dst_name is None or not convert_supported(info.dtype, dst_name):
+            raise err.Unsupported(
+                f"safetensors: tensor {name!r}: cannot load {info.dtype} "
+                f"into {tensor.dtype}")
+        if tensor.numel():
+            self._execute(
+                [self._request(info, dst_name, shard, tensor.data_ptr())],
+                tensor.device)
+
+    def close(self) -> None:
+        self.reader.close()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def load_file(sync_fs, path: str, device="cuda:0", dtype=None) -> dict:
+    """One-shot: cached safetensors path -> {name: tensor}."""
+    with CurvineSafetensors(sync_fs, path) as f:
+        return f.load(device=device, dtype=dtype)

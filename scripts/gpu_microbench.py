@@ -73,8 +73,164 @@ def bench_lz4(a, rng, results):
     results["lz4_compress_then_d2h_beats_raw_d2h"] = bool(t_lz4 < t_raw)
 
 
+def _stats(ts):
+    ts = sorted(ts)
+    return {"median_us": round(float(np.median(ts)) * 1e6, 1),
+            "min_us": round(ts[0] * 1e6, 1), "max_us": round(ts[-1] * 1e6, 1),
+            "stdev_us": round(float(np.std(ts, ddof=1)) * 1e6, 1),
+            "repeats": len(ts)}
+
+
+def _alternate(fns, repeats=15, inner=8, warmup=3):
+    """Time several callables in the same run, alternating them; every
+    sample is `inner` back-to-back calls (each ends in a device sync)."""
+    for _ in range(warmup):
+        for fn in fns:
+            fn()
+    out = [[] for _ in fns]
+    for _ in range(repeats):
+        for i, fn in enumerate(fns):
+            t0 = time.perf_counter()
+            for _ in range(inner):
+                fn()
+            out[i].append((time.perf_counter() - t0) / inner)
+    return [_stats(ts) for ts in out]
+
+
+def bench_safetensors(results):
+    """Typed loads out of the HBM arena (convert_segments_kernel) against
+    what the same user does without it; see profiles/safetensors_load.json."""
+    import tempfile
+
+    import torch
+    D = native.DTYPES
+    n_el = 64 << 20
+    a = native.Arena(0, (256 << 20) + (1 << 20))
+    rng = np.random.default_rng(3)
+    chunk = rng.integers(0, 2 ** 32, 4 << 20, dtype=np.uint32)
+    chunk &= np.uint32(0xBFFFFFFF)
+    for i in range(0, 256 << 20, chunk.nbytes):
+        a.write(i, chunk.tobytes())
+    a.write(256 << 20, b"\0" * 64)
+    dev = torch.device("cuda:0")
+
+    def fused_f32_bf16(off=0):
+        out = torch.empty(n_el, dtype=torch.bfloat16, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        a.convert_ptr([(off, out.data_ptr(), 1, n_el, n_el * 4,
+                        D["F32"], D["BF16"])])
+        return out
+
+    def two_pass_f32_bf16():
+        tmp = torch.empty(n_el * 4, dtype=torch.uint8, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        a.read_to_ptr(0, tmp.data_ptr(), n_el * 4, True)
+        out = tmp.view(torch.float32).to(torch.bfloat16)
+        torch.cuda.synchronize(dev)
+        return out
+
+    assert torch.equal(fused_f32_bf16().view(torch.int16),
+                       two_pass_f32_bf16().view(torch.int16))
+    fused, two = _alternate([fused_f32_bf16, two_pass_f32_bf16])
+    ratio = fused["median_us"] / two["median_us"]
+    results["f32_to_bf16_64Mi"] = {
+        "fused": fused, "two_pass_d2d_then_torch_cast": two,
+        "fused_over_two_pass": round(ratio, 3),
+        "fused_GBps_rd_plus_wr": round(n_el * 6 / fused["median_us"] / 1e3, 1),
+        "bar_fused_not_slower_than_two_pass_plus_its_stdev": bool(
+            fused["median_us"] <= two["median_us"] + two["stdev_us"])}
+
+    nb = n_el * 2
+
+    def same_bf16(off):
+        def run():
+            out = torch.empty(n_el, dtype=torch.bfloat16, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            a.convert_ptr([(off, out.data_ptr(), 1, n_el, nb,
+                            D["BF16"], D["BF16"])])
+            return out
+        return run
+
+    def d2d(off):
+        def run():
+            out = torch.empty(n_el, dtype=torch.bfloat16, device=dev)
+            torch.cuda.current_stream(dev).synchronize()
+            a.read_to_ptr(off, out.data_ptr(), nb, True)
+            torch.cuda.synchronize(dev)
+            return out
+        return run
+
+    for tag, off in (("aligned", 0), ("odd_offset", 1)):
+        assert torch.equal(same_bf16(off)().view(torch.int16),
+                           d2d(off)().view(torch.int16))
+        k, c = _alternate([same_bf16(off), d2d(off)])
+        results[f"bf16_copy_64Mi_{tag}"] = {
+            "convert_ptr": k, "read_to_ptr_d2d": c,
+            "convert_over_d2d": round(k["median_us"] / c["median_us"], 3),
+            "convert_GBps_rd_plus_wr": round(
+                2 * nb / k["median_us"] / 1e3, 1)}
+    a.close()
+
+    # 300-tensor file through the whole stack: batched load() against a
+    # loop of get_tensor()
+    import json as _json
+    import struct
+
+    from curvine_amd.client.filesystem import SyncFs
+    from curvine_amd.sdk import CurvineSafetensors
+    from curvine_amd.testing import SyncMiniCluster, test_conf
+    hdr, parts, pos = {}, [], 0
+    for i in range(300):
+        shape = (1024, 2048) if i % 15 == 0 else (8192,)
+        dt = "BF16" if i % 15 == 0 else "F32"
+        nbytes = int(np.prod(shape)) * (2 if dt == "BF16" else 4)
+        raw = rng.integers(0, 256, nbytes, dtype=np.uint8)
+        raw[1::2] &= 0xBF
+        hdr[f"layer{i:03d}.w"] = {"dtype": dt, "shape": list(shape),
+                                  "data_offsets": [pos, pos + nbytes]}
+        parts.append(raw.tobytes())
+        pos += nbytes
+    js = _json.dumps(hdr).encode()
+    js += b" " * (-(len(js) + 8) % 64)      # aligned data section
+    blob = struct.pack("<Q", len(js)) + js + b"".join(parts)
+    tmp = tempfile.mkdtemp(prefix="curvine-stbench-")
+    conf = test_conf(tmp)
+    conf.master.block_size = conf.client.block_size = 64 << 20
+    smc = SyncMiniCluster(conf=conf, tmp_dir=tmp,
+                          worker_dirs=[["[HBM:1GB:0]gpu0"]]).start()
+    try:
+        sf = SyncFs(smc.client_conf())
+        sf.write_file("/bench/m.safetensors", blob, storage_tier="HBM")
+        f = CurvineSafetensors(sf, "/bench/m.safetensors")
+
+        def batched():
+            return f.load(device="cuda:0", dtype=torch.bfloat16)
+
+        def looped():
+            return {k: f.get_tensor(k, "cuda:0", torch.bfloat16)
+                    for k in f.keys()}
+        b_out, l_out = batched(), looped()
+        assert all(torch.equal(b_out[k].view(torch.int16),
+                               l_out[k].view(torch.int16)) for k in b_out)
+        del b_out, l_out
+        b, lp = _alternate([batched, looped], repeats=9, inner=2, warmup=2)
+        results["file_300_tensors"] = {
+            "file_bytes": len(blob), "batched_load": b,
+            "get_tensor_loop": lp,
+            "batched_over_loop": round(b["median_us"] / lp["median_us"], 3)}
+        f.close()
+        sf.shutdown()
+    finally:
+        smc.stop()
+
+
 def main():
     assert native.gpu_available(), "needs a GPU"
+    if "--safetensors-only" in sys.argv[1:]:
+        results = {}
+        bench_safetensors(results)
+        print(json.dumps(results, indent=1))
+        return
     if "--lz4-only" in sys.argv[1:]:
         a = native.Arena(0, (512 << 20) + (1 << 20), staging_bytes=16 << 20,
                          staging_count=8)
@@ -155,9 +311,10 @@ def main():
 
     bench_lz4(a, rng, results)
 
-    print(json.dumps(results, indent=1))
     a.close()
     pin.close()
+    bench_safetensors(results)
+    print(json.dumps(results, indent=1))
 
 
 if __name__ == "__main__":
