@@ -152,41 +152,60 @@ extern "C" __global__ __launch_bounds__(64) void lz4_decompress_kernel(
                        raw_size - (uint64_t)c * chunk_size);
     uint32_t si = 0, di = 0;
     int lane = threadIdx.x;
+    // The checks are those of lz4_decompress_block_host, in the same
+    // order.  Every lane parses the same bytes, so each check, and the
+    // return it leads to, is wave-uniform.  Lengths are summed in 64 bits:
+    // a run of 255s cannot wrap a bound.
+    bool bad = false;
     while (si < comp_n) {
       // every lane parses the same header (uniform addresses broadcast)
       uint8_t tok = src[si++];
-      uint32_t lit = tok >> 4;
+      uint64_t lit = tok >> 4;
       if (lit == 15) {
         uint8_t b;
-        do { b = src[si++]; lit += b; } while (b == 255);
+        do {
+          if (si >= comp_n) { bad = true; break; }
+          b = src[si++]; lit += b;
+        } while (b == 255);
       }
-      if (di + lit > cap || si + lit > comp_n) {
-        if (lane == 0) atomicExch(error_flag, 1 + (int)c);
-        return;
+      if (bad || (uint64_t)di + lit > cap || (uint64_t)si + lit > comp_n) {
+        bad = true;
+        break;
       }
-      for (uint32_t i = lane; i < lit; i += 64) dst[di + i] = src[si + i];
+      for (uint32_t i = lane; i < (uint32_t)lit; i += 64)
+        dst[di + i] = src[si + i];
       __threadfence_block();   // cross-lane visibility of the writes
-      di += lit; si += lit;
+      di += (uint32_t)lit; si += (uint32_t)lit;
       if (si >= comp_n) break;
+      if ((uint64_t)si + 2 > comp_n) { bad = true; break; }
       uint32_t off = src[si] | (src[si + 1] << 8);
       si += 2;
-      uint32_t mlen = (tok & 0xF);
+      uint64_t mlen = (tok & 0xF);
       if (mlen == 15) {
         uint8_t b;
-        do { b = src[si++]; mlen += b; } while (b == 255);
+        do {
+          if (si >= comp_n) { bad = true; break; }
+          b = src[si++]; mlen += b;
+        } while (b == 255);
       }
       mlen += 4;
-      if (off == 0 || off > di || di + mlen > cap) {
-        if (lane == 0) atomicExch(error_flag, 1 + (int)c);
-        return;
+      if (bad || off == 0 || off > di || (uint64_t)di + mlen > cap) {
+        bad = true;
+        break;
       }
       // match bytes are periodic with period `off`: every lane reads only
       // PRE-MATCH data (dst[di-off .. di)), so there is no intra-match
       // hazard for any offset
-      for (uint32_t i = lane; i < mlen; i += 64)
+      for (uint32_t i = lane; i < (uint32_t)mlen; i += 64)
         dst[di + i] = dst[di - off + (i % off)];
       __threadfence_block();
-      di += mlen;
+      di += (uint32_t)mlen;
+    }
+    // a chunk that decodes short leaves stale bytes in the block: the host
+    // decoder's `got != cap`
+    if (bad || di != cap) {
+      if (lane == 0) atomicExch(error_flag, 1 + (int)c);
+      return;
     }
   }
 }

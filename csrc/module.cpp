@@ -672,21 +672,9 @@ static void arena_fill(int h, uint64_t off, uint64_t n, int value) {
   HIP_CHECK(hipStreamSynchronize(a->kstream));
 }
 
-static uint32_t arena_crc32c(int h, uint64_t off, uint64_t n) {
-  Arena* a = get_arena(h);
-  check_range(a, off, n);
-  if (!a->is_dev()) {
-    const uint8_t* p = (const uint8_t*)a->base + off;
-    py::gil_scoped_release rel;
-    crc_init_tables();
-    return crc32c_sw(p, n, 0);
-  }
-  py::gil_scoped_release rel;
-  std::lock_guard<std::mutex> g(a->mu);
-  HIP_CHECK(hipSetDevice(a->device));
-  ensure_crc_tables(a);
-  const uint8_t* p = (const uint8_t*)a->base + off;
-  if (((uintptr_t)p & 7) != 0) throw std::runtime_error("crc32c needs 8B-aligned offset");
+// crc32c of n device bytes at an 8 B-aligned p (the kernel reads 8 B words);
+// caller holds a->mu and has set the device
+static uint32_t dev_crc32c_aligned(Arena* a, const uint8_t* p, uint64_t n) {
   uint64_t n_sub = n / CRC_SUB;
   uint64_t tail = n - n_sub * CRC_SUB;
   uint32_t result = 0;
@@ -727,6 +715,33 @@ static uint32_t arena_crc32c(int h, uint64_t off, uint64_t n) {
     result = n_sub ? crc32c_combine(result, tail_crc, tail) : tail_crc;
   }
   return result;
+}
+
+static uint32_t arena_crc32c(int h, uint64_t off, uint64_t n) {
+  Arena* a = get_arena(h);
+  check_range(a, off, n);
+  if (!a->is_dev()) {
+    const uint8_t* p = (const uint8_t*)a->base + off;
+    py::gil_scoped_release rel;
+    crc_init_tables();
+    return crc32c_sw(p, n, 0);
+  }
+  py::gil_scoped_release rel;
+  std::lock_guard<std::mutex> g(a->mu);
+  HIP_CHECK(hipSetDevice(a->device));
+  ensure_crc_tables(a);
+  const uint8_t* p = (const uint8_t*)a->base + off;
+  // any byte offset: the up-to-7 bytes before the next 8 B boundary are
+  // read back and checksummed here, the aligned rest goes to the kernel
+  uint64_t head = std::min<uint64_t>((8 - ((uintptr_t)p & 7)) & 7, n);
+  if (!head) return dev_crc32c_aligned(a, p, n);
+  uint8_t hb[8];
+  HIP_CHECK(hipMemcpyAsync(hb, p, head, hipMemcpyDeviceToHost, a->kstream));
+  HIP_CHECK(hipStreamSynchronize(a->kstream));
+  uint32_t head_crc = crc32c_sw(hb, head, 0);
+  if (head == n) return head_crc;
+  return crc32c_combine(head_crc, dev_crc32c_aligned(a, p + head, n - head),
+                        n - head);
 }
 
 static uint32_t crc32c_buf(py::buffer buf, uint32_t init) {
@@ -773,9 +788,12 @@ static void arena_gather(int h, std::vector<std::pair<uint64_t, uint64_t>> ext,
     }
     o += ext[i].second;
   }
+  if (tile_ext.empty()) return;   // nothing to copy: no grid-0 launch
   size_t meta = exts.size() * sizeof(Extent) +
                 tile_ext.size() * (sizeof(uint32_t) + sizeof(uint64_t));
-  ensure_scratch(a, total + meta + 64);
+  // slack: up to 63 B to round `total` up to the extent table, up to 4 B
+  // to align the tile offsets
+  ensure_scratch(a, total + meta + 128);
   uint8_t* d_pack = (uint8_t*)a->scratch;
   Extent* d_ext = (Extent*)(d_pack + ((total + 63) & ~63ull));
   uint32_t* d_te = (uint32_t*)(d_ext + exts.size());
@@ -849,6 +867,7 @@ static void arena_gather_ptr(
       tile_off.push_back(t);
     }
   }
+  if (tile_ext.empty()) return;   // nothing to copy: no grid-0 launch
   size_t meta = exts.size() * sizeof(Extent) +
                 tile_ext.size() * (sizeof(uint32_t) + sizeof(uint64_t)) + 64;
   ensure_scratch(a, meta);
@@ -1215,6 +1234,7 @@ static uint64_t arena_lz4_decompress(int ah, uint64_t dst_off, py::buffer buf) {
   size_t n = (size_t)info.size * info.itemsize;
   Lz4Header h = lz4_parse(src, n);
   check_range(a, dst_off, h.raw_size);
+  if (h.n_chunks == 0) return 0;   // empty container: no grid-0 launch
   py::gil_scoped_release rel;
   if (!a->is_dev()) {
     const uint8_t* p = h.payload;
