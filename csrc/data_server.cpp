@@ -315,7 +315,7 @@ static void data_forward(DataServer* S, const std::shared_ptr<DataConn>& c,
   }
 }
 
-// The pinned bounce pool (BouncePair/bounce_acquire/bounce_release) is
+// The pinned bounce pool and the D2H pipeline over it (d2h_pipeline) are
 // shared module infrastructure — defined in module.cpp ahead of the
 // arena copy engines, used here for HBM stream serving.
 
@@ -385,58 +385,17 @@ static bool data_serve_read(DataServer* S, DataConn* c, const uint8_t* frame,
         pos += cn;
       }
     } else {
-      // HBM: double-buffered D2H into pooled pinned bounce buffers,
-      // overlapping the socket sends
-      HIP_CHECK(hipSetDevice(a->device));
-      hipStream_t s = thread_stream(a->device);
-      size_t bsz = std::min<int64_t>(chunk, kBounceSz);
-      BouncePair* bp = bounce_acquire(a->device);
-      struct BounceGuard {
-        BouncePair* b;
-        hipStream_t s;
-        ~BounceGuard() {
-          // an exception can leave an async D2H in flight targeting the
-          // pinned buffers: drain before the pair goes back to the pool
-          hipStreamSynchronize(s);
-          bounce_release(b);
-        }
-      } bg{bp, s};
-      void** pin = bp->pin;
-      hipEvent_t* ev = bp->ev;
-      const uint8_t* src = (const uint8_t*)a->base + b->aoff + offset;
-      int64_t nchunks = (n + bsz - 1) / int64_t(bsz);
-      for (int64_t k = 0; k < nchunks && ok; k++) {
-        int64_t coff = k * int64_t(bsz);
-        int64_t cn = std::min<int64_t>(bsz, n - coff);
-        int slot = int(k & 1);
-        HIP_CHECK(hipMemcpyAsync(pin[slot], src + coff, cn,
-                                 hipMemcpyDeviceToHost, s));
-        HIP_CHECK(hipEventRecord(ev[slot], s));
-        if (k > 0) {
-          // previous chunk's copy has completed by FIFO stream order;
-          // but sync its event explicitly before touching the buffer
-          int prev = int((k - 1) & 1);
-          HIP_CHECK(hipEventSynchronize(ev[prev]));
-          int64_t poff = (k - 1) * int64_t(bsz);
-          int64_t pn = std::min<int64_t>(bsz, n - poff);
-          std::string ph = meta_proto(0, uint32_t(pn), kCodeReadBlock,
-                                      uint8_t((2 << 4) | req_status), req_id,
-                                      seq);
-          ok = frame_send_locked(c->fd, ph, (const uint8_t*)pin[prev],
-                                 size_t(pn));
-        }
-      }
-      if (ok && nchunks > 0) {
-        int last = int((nchunks - 1) & 1);
-        HIP_CHECK(hipEventSynchronize(ev[last]));
-        int64_t poff = (nchunks - 1) * int64_t(bsz);
-        int64_t pn = n - poff;
-        std::string ph = meta_proto(0, uint32_t(pn), kCodeReadBlock,
-                                    uint8_t((2 << 4) | req_status), req_id,
-                                    seq);
-        ok = frame_send_locked(c->fd, ph, (const uint8_t*)pin[last],
-                               size_t(pn));
-      }
+      // HBM: the pooled pinned D2H pipeline (module.cpp), one frame per
+      // chunk, so the copies overlap the socket sends
+      ok = d2h_pipeline(
+          a, (const uint8_t*)a->base + b->aoff + offset, uint64_t(n),
+          uint64_t(std::min<int64_t>(chunk, kBounceSz)),
+          [&](const uint8_t* pin, uint64_t, uint64_t pn) {
+            std::string ph = meta_proto(0, uint32_t(pn), kCodeReadBlock,
+                                        uint8_t((2 << 4) | req_status), req_id,
+                                        seq);
+            return frame_send_locked(c->fd, ph, pin, size_t(pn));
+          });
     }
   } else if (b->direct) {
     // NVMe page-cache bypass: aligned O_DIRECT preads into an aligned

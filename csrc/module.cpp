@@ -20,6 +20,7 @@
 
 #include <atomic>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -28,6 +29,11 @@
 #include <hip/hip_runtime.h>
 
 namespace py = pybind11;
+
+// Kernels live in this translation unit (device symbols + hipMemcpyToSymbol
+// need no -fgpu-rdc this way).  kernels.hip comes first: it owns WG and
+// CRC_SUB, which the host CRC tables below are built from.
+#include "kernels.hip"
 
 #define HIP_CHECK(expr)                                                        \
   do {                                                                         \
@@ -44,8 +50,6 @@ namespace py = pybind11;
 static uint32_t crc_tab[8][256];
 static uint32_t comb_mat[24][32];  // shift by (CRC_SUB << k) bytes
 static const uint32_t CRC_POLY = 0x82F63B78u;  // reflected Castagnoli
-static const int CRC_SUB = 4096;
-static const int WG = 256;
 
 static void gf2_square(uint32_t dst[32], const uint32_t src[32]) {
   for (int i = 0; i < 32; ++i) {
@@ -91,7 +95,15 @@ static void crc_init_tables() {
   for (int k = 1; k < 24; ++k) gf2_square(comb_mat[k], comb_mat[k - 1]);
 }
 
+// built once, before the first reader: every host CRC goes through
+// crc32c_sw, and the device upload calls this before it copies the tables
+static void crc_host_tables() {
+  static std::once_flag once;
+  std::call_once(once, crc_init_tables);
+}
+
 static uint32_t crc32c_sw(const uint8_t* p, size_t n, uint32_t crc_in) {
+  crc_host_tables();
   uint32_t crc = crc_in ^ 0xFFFFFFFFu;
   while (n && ((uintptr_t)p & 7)) { crc = (crc >> 8) ^ crc_tab[0][(crc ^ *p++) & 0xFF]; --n; }
 #if defined(__SSE4_2__)
@@ -135,11 +147,6 @@ static uint32_t crc32c_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
   return crc32c_shift(crc1, len2) ^ crc2;
 }
 
-// ---------------------------------------------------------------------------
-// Kernels — single translation unit (device symbols + hipMemcpyToSymbol
-// need no -fgpu-rdc this way)
-// ---------------------------------------------------------------------------
-#include "kernels.hip"
 #include "lz4.hip"
 #include "tensor_cast.hip"
 
@@ -161,8 +168,6 @@ static int device_count() {
 // Arena
 // ---------------------------------------------------------------------------
 
-#define SPOOL 16  // parallel copy streams per device arena
-
 struct Arena {
   void* base = nullptr;
   size_t cap = 0;
@@ -170,11 +175,6 @@ struct Arena {
   bool pinned = false;   // host arena allocated with hipHostMalloc
   hipStream_t stream = nullptr;       // copy stream
   hipStream_t kstream = nullptr;      // kernel stream
-  // stream pool: concurrent readers each grab a slot so large copies
-  // don't serialize on one stream/lock
-  hipStream_t spool[SPOOL] = {};
-  std::mutex spool_mu[SPOOL];
-  std::atomic<uint32_t> srr{0};
   // pinned staging ring (device arenas)
   std::vector<void*> pin;
   std::vector<hipEvent_t> ev;
@@ -182,13 +182,43 @@ struct Arena {
   // device scratch for gather/crc results
   void* scratch = nullptr;
   size_t scratch_sz = 0;
-  bool crc_tables_uploaded = false;
   // true when base came from hipIpcOpenMemHandle (another process's
   // arena): destroy closes the mapping instead of freeing
   bool ipc_imported = false;
   std::mutex mu;
 
+  Arena(int device_, size_t cap_) : cap(cap_), device(device_) {}
+  Arena(const Arena&) = delete;
+  Arena& operator=(const Arena&) = delete;
+
   bool is_dev() const { return device >= 0; }
+
+  void open_streams() {
+    HIP_CHECK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    HIP_CHECK(hipStreamCreateWithFlags(&kstream, hipStreamNonBlocking));
+  }
+
+  // frees whatever exists, so an arena that failed half-way through its
+  // construction unwinds through here too
+  ~Arena() {
+    if (is_dev()) {
+      hipSetDevice(device);
+      if (stream) hipStreamSynchronize(stream);
+      for (auto* p : pin) if (p) hipHostFree(p);
+      for (auto e : ev) if (e) hipEventDestroy(e);
+      if (scratch) hipFree(scratch);
+      if (base) {
+        if (ipc_imported) hipIpcCloseMemHandle(base);
+        else hipFree(base);
+      }
+      if (stream) hipStreamDestroy(stream);
+      if (kstream) hipStreamDestroy(kstream);
+    } else if (pinned) {
+      hipHostFree(base);
+    } else {
+      std::free(base);
+    }
+  }
 };
 
 static std::vector<Arena*> g_arenas;
@@ -201,22 +231,25 @@ static Arena* get_arena(int h) {
   return g_arenas[h];
 }
 
+// hand a finished arena to the handle table (first free slot)
+static int arena_register(std::unique_ptr<Arena> a) {
+  std::lock_guard<std::mutex> g(g_arenas_mu);
+  size_t i = 0;
+  while (i < g_arenas.size() && g_arenas[i]) ++i;
+  if (i == g_arenas.size()) g_arenas.push_back(nullptr);
+  g_arenas[i] = a.release();
+  return (int)i;
+}
+
 static int arena_create(int device, size_t cap, size_t staging_bytes,
                         int staging_count, bool host_pinned) {
-  auto* a = new Arena();
-  a->device = device;
-  a->cap = cap;
+  if (device >= 0 && device >= device_count())
+    throw std::runtime_error("no such GPU device");
+  auto a = std::make_unique<Arena>(device, cap);
   if (device >= 0) {
-    if (device >= device_count()) {
-      delete a;
-      throw std::runtime_error("no such GPU device");
-    }
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipMalloc(&a->base, cap));
-    HIP_CHECK(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamCreateWithFlags(&a->kstream, hipStreamNonBlocking));
-    for (int i = 0; i < SPOOL; ++i)
-      HIP_CHECK(hipStreamCreateWithFlags(&a->spool[i], hipStreamNonBlocking));
+    a->open_streams();
     a->pin_sz = staging_bytes;
     a->pin.resize(staging_count);
     a->ev.resize(staging_count);
@@ -235,21 +268,16 @@ static int arena_create(int device, size_t cap, size_t staging_bytes,
       // faulting straight onto huge pages gets the fast path from the
       // first write
       size_t aligned = (cap + ((2u << 20) - 1)) & ~size_t((2u << 20) - 1);
-      if (posix_memalign(&a->base, 2u << 20, aligned) != 0) {
-        delete a;
-        throw std::bad_alloc();
-      }
+      void* p = nullptr;
+      if (posix_memalign(&p, 2u << 20, aligned) != 0) throw std::bad_alloc();
+      a->base = p;
 #ifdef MADV_HUGEPAGE
       madvise(a->base, aligned, MADV_HUGEPAGE);
 #endif
       std::memset(a->base, 0, cap);
     }
   }
-  std::lock_guard<std::mutex> g(g_arenas_mu);
-  for (size_t i = 0; i < g_arenas.size(); ++i)
-    if (!g_arenas[i]) { g_arenas[i] = a; return (int)i; }
-  g_arenas.push_back(a);
-  return (int)g_arenas.size() - 1;
+  return arena_register(std::move(a));
 }
 
 static void arena_destroy(int h) {
@@ -259,23 +287,6 @@ static void arena_destroy(int h) {
     if (h < 0 || h >= (int)g_arenas.size() || !g_arenas[h]) return;
     a = g_arenas[h];
     g_arenas[h] = nullptr;
-  }
-  if (a->is_dev()) {
-    hipSetDevice(a->device);
-    hipStreamSynchronize(a->stream);
-    for (auto* p : a->pin) hipHostFree(p);
-    for (auto e : a->ev) hipEventDestroy(e);
-    if (a->scratch) hipFree(a->scratch);
-    if (a->ipc_imported) hipIpcCloseMemHandle(a->base);
-    else hipFree(a->base);
-    hipStreamDestroy(a->stream);
-    hipStreamDestroy(a->kstream);
-    for (int i = 0; i < SPOOL; ++i)
-      if (a->spool[i]) hipStreamDestroy(a->spool[i]);
-  } else if (a->pinned) {
-    hipHostFree(a->base);
-  } else {
-    std::free(a->base);
   }
   delete a;
 }
@@ -305,43 +316,75 @@ static int arena_ipc_open(py::bytes handle, size_t cap, int device) {
     throw std::runtime_error("ipc open: bad device");
   hipIpcMemHandle_t ih;
   std::memcpy(&ih, hb.data(), sizeof(ih));
-  auto* a = new Arena();
-  a->device = device;
-  a->cap = cap;
+  auto a = std::make_unique<Arena>(device, cap);
   a->ipc_imported = true;
   HIP_CHECK(hipSetDevice(device));
   hipError_t e = hipIpcOpenMemHandle(&a->base, ih,
                                      hipIpcMemLazyEnablePeerAccess);
   if (e != hipSuccess) {
-    delete a;
+    a->base = nullptr;   // nothing was mapped: nothing to close
     throw std::runtime_error(std::string("hipIpcOpenMemHandle: ") +
                              hipGetErrorString(e));
   }
-  HIP_CHECK(hipStreamCreateWithFlags(&a->stream, hipStreamNonBlocking));
-  HIP_CHECK(hipStreamCreateWithFlags(&a->kstream, hipStreamNonBlocking));
-  for (int i = 0; i < SPOOL; ++i)
-    HIP_CHECK(hipStreamCreateWithFlags(&a->spool[i], hipStreamNonBlocking));
+  a->open_streams();
   // no staging ring: reads ride the pooled bounce pairs / pinned dests
-  std::lock_guard<std::mutex> g(g_arenas_mu);
-  for (size_t i = 0; i < g_arenas.size(); ++i)
-    if (!g_arenas[i]) { g_arenas[i] = a; return (int)i; }
-  g_arenas.push_back(a);
-  return (int)g_arenas.size() - 1;
+  return arena_register(std::move(a));
 }
 
 static void ensure_scratch(Arena* a, size_t n) {
   if (a->scratch_sz >= n) return;
-  if (a->scratch) HIP_CHECK(hipFree(a->scratch));
+  if (a->scratch) {
+    // forget the old block before freeing it, so a failing hipMalloc
+    // below leaves no dangling pointer for ~Arena to free again
+    void* old = a->scratch;
+    a->scratch = nullptr;
+    a->scratch_sz = 0;
+    HIP_CHECK(hipFree(old));
+  }
   HIP_CHECK(hipMalloc(&a->scratch, n));
   a->scratch_sz = n;
 }
 
-static void ensure_crc_tables(Arena* a) {
-  if (a->crc_tables_uploaded) return;
-  crc_init_tables();
+// Bump carver over the arena's device scratch: sized once up front (the
+// only ensure_scratch of a call, so no pointer outlives a regrow), then
+// hands out typed sub-ranges.  Byte regions start on 64 B, tables on their
+// natural alignment; room<T>() is what take<T>() can cost at worst.
+// Caller holds a->mu.
+struct Scratch {
+  uint8_t* p;
+  uint8_t* end;
+  Scratch(Arena* a, size_t bytes) {
+    ensure_scratch(a, bytes);
+    p = (uint8_t*)a->scratch;
+    end = p + bytes;
+  }
+  template <class T> static constexpr size_t align() {
+    return sizeof(T) == 1 ? 64 : alignof(T);
+  }
+  template <class T> static size_t room(size_t n) {
+    return n * sizeof(T) + align<T>() - 1;
+  }
+  template <class T> T* take(size_t n) {
+    uintptr_t at = ((uintptr_t)p + align<T>() - 1) & ~(uintptr_t)(align<T>() - 1);
+    p = (uint8_t*)at + n * sizeof(T);
+    if (p > end) throw std::logic_error("scratch carve exceeds its sizing");
+    return (T*)at;
+  }
+};
+
+// g_crc_tab / g_comb_mat are per-device symbols: upload once per device,
+// under a lock of their own, so no arena re-uploads them under another
+// arena's running CRC kernel.  Caller has set the device.
+static void ensure_crc_tables(int device) {
+  static std::mutex mu;
+  static std::vector<char> uploaded;
+  std::lock_guard<std::mutex> g(mu);
+  if ((size_t)device < uploaded.size() && uploaded[device]) return;
+  crc_host_tables();
   HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_crc_tab), crc_tab, sizeof(crc_tab)));
   HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_comb_mat), comb_mat, sizeof(comb_mat)));
-  a->crc_tables_uploaded = true;
+  if ((size_t)device >= uploaded.size()) uploaded.resize(device + 1);
+  uploaded[device] = 1;
 }
 
 // ---- host<->arena copies with pinned-ring pipelining ----
@@ -360,7 +403,7 @@ static bool is_pinned_host(const void* p) {
 }
 
 // small or pinned-destination copies skip the ring: one hipMemcpyAsync on
-// a pooled stream (parallel across caller threads, no global lock)
+// the caller's thread stream (parallel across caller threads, no global lock)
 static const uint64_t RING_THRESHOLD = 2u << 20;
 
 // ------------------------------------------------------- pinned bounce pool
@@ -462,52 +505,65 @@ static void dev_write_direct(Arena* a, uint64_t off, const uint8_t* src,
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
-// device -> host buffer, chunked through the pinned ring: D2H DMA of chunk
-// k overlaps the CPU memcpy of chunk k-1 (the staging pipeline of
-// BASELINE.json's "pinned hipMemcpyAsync on a side stream").
-// device -> unpinned host, chunked through a POOLED pinned double-buffer
-// on the caller's stream (D2H DMA of chunk k overlaps the memcpy-out of
-// chunk k-1); concurrent readers no longer serialize on one arena ring.
+// A pooled bounce pair on the caller's thread stream.  Going out of scope
+// drains the stream first: no in-flight DMA may outlive the pair's turn.
+struct BounceLease {
+  hipStream_t s;
+  BouncePair* bp;
+  explicit BounceLease(int device)
+      : s(thread_stream(device)), bp(bounce_acquire(device)) {}
+  BounceLease(const BounceLease&) = delete;
+  BounceLease& operator=(const BounceLease&) = delete;
+  ~BounceLease() {
+    (void)hipStreamSynchronize(s);
+    bounce_release(bp);
+  }
+};
+
+// device -> host in chunks of `cs` (<= kBounceSz) through a POOLED pinned
+// double-buffer on the caller's stream: the D2H DMA of chunk k overlaps
+// sink(pinned, offset, len) of chunk k-1, and concurrent readers do not
+// serialize on one arena ring.  Chunks reach the sink in order; a sink
+// returning false stops the pipeline, which then returns false.
+template <class Sink>
+static bool d2h_pipeline(Arena* a, const uint8_t* src, uint64_t n, uint64_t cs,
+                         Sink&& sink) {
+  HIP_CHECK(hipSetDevice(a->device));
+  BounceLease l(a->device);
+  uint64_t nchunks = (n + cs - 1) / cs;
+  for (uint64_t c = 0; c <= nchunks; ++c) {
+    if (c < nchunks) {
+      uint64_t coff = c * cs;
+      HIP_CHECK(hipMemcpyAsync(l.bp->pin[c & 1], src + coff,
+                               std::min<uint64_t>(cs, n - coff),
+                               hipMemcpyDeviceToHost, l.s));
+      HIP_CHECK(hipEventRecord(l.bp->ev[c & 1], l.s));
+    }
+    if (c > 0) {
+      // drain the previous chunk while this one is in flight
+      uint64_t poff = (c - 1) * cs;
+      HIP_CHECK(hipEventSynchronize(l.bp->ev[(c - 1) & 1]));
+      if (!sink((const uint8_t*)l.bp->pin[(c - 1) & 1], poff,
+                std::min<uint64_t>(cs, n - poff)))
+        return false;
+    }
+  }
+  return true;
+}
+
+// device -> unpinned host through the bounce pipeline, memcpy as the sink
 static void dev_read(Arena* a, uint64_t off, uint8_t* dst, uint64_t n) {
   if (n <= RING_THRESHOLD || is_pinned_host(dst)) {
     dev_read_direct(a, off, dst, n);
     return;
   }
-  HIP_CHECK(hipSetDevice(a->device));
-  BouncePair* bp = bounce_acquire(a->device);
-  hipStream_t s = thread_stream(a->device);
-  const uint8_t* src = (const uint8_t*)a->base + off;
   uint64_t cs = std::min<uint64_t>(kBounceSz,
                                    std::max<uint64_t>(1u << 20, (n + 1) / 2));
-  uint64_t nchunks = (n + cs - 1) / cs;
-  try {
-    for (uint64_t c = 0; c < nchunks; ++c) {
-      uint64_t coff = c * cs;
-      uint64_t clen = std::min<uint64_t>(cs, n - coff);
-      int slot = (int)(c & 1);
-      HIP_CHECK(hipMemcpyAsync(bp->pin[slot], src + coff, clen,
-                               hipMemcpyDeviceToHost, s));
-      HIP_CHECK(hipEventRecord(bp->ev[slot], s));
-      if (c > 0) {
-        // drain the previous chunk while this one is in flight
-        int prev = (int)((c - 1) & 1);
-        HIP_CHECK(hipEventSynchronize(bp->ev[prev]));
-        uint64_t poff = (c - 1) * cs;
-        std::memcpy(dst + poff, bp->pin[prev],
-                    std::min<uint64_t>(cs, n - poff));
-      }
-    }
-    int last = (int)((nchunks - 1) & 1);
-    HIP_CHECK(hipEventSynchronize(bp->ev[last]));
-    uint64_t loff = (nchunks - 1) * cs;
-    std::memcpy(dst + loff, bp->pin[last],
-                std::min<uint64_t>(cs, n - loff));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);   // no in-flight DMA may outlive bp
-    bounce_release(bp);
-    throw;
-  }
-  bounce_release(bp);
+  d2h_pipeline(a, (const uint8_t*)a->base + off, n, cs,
+               [dst](const uint8_t* pin, uint64_t coff, uint64_t clen) {
+                 std::memcpy(dst + coff, pin, clen);
+                 return true;
+               });
 }
 
 // host -> device, chunked through a POOLED pinned double-buffer on the
@@ -520,32 +576,25 @@ static void dev_write(Arena* a, uint64_t off, const uint8_t* src, uint64_t n) {
     return;
   }
   HIP_CHECK(hipSetDevice(a->device));
-  BouncePair* bp = bounce_acquire(a->device);
-  hipStream_t s = thread_stream(a->device);
+  BounceLease l(a->device);
   uint8_t* dst = (uint8_t*)a->base + off;
   // chunk so every call gets >= 2 chunks: the staging memcpy of chunk
   // k overlaps the H2D DMA of chunk k-1 even for a single 4 MiB write
   uint64_t cs = std::min<uint64_t>(kBounceSz,
                                    std::max<uint64_t>(1u << 20, (n + 1) / 2));
   uint64_t nchunks = (n + cs - 1) / cs;
-  try {
-    for (uint64_t c = 0; c < nchunks; ++c) {
-      uint64_t coff = c * cs;
-      uint64_t clen = std::min<uint64_t>(cs, n - coff);
-      int slot = (int)(c & 1);
-      if (c >= 2) HIP_CHECK(hipEventSynchronize(bp->ev[slot]));
-      std::memcpy(bp->pin[slot], src + coff, clen);
-      HIP_CHECK(hipMemcpyAsync(dst + coff, bp->pin[slot], clen,
-                               hipMemcpyHostToDevice, s));
-      HIP_CHECK(hipEventRecord(bp->ev[slot], s));
-    }
-    HIP_CHECK(hipStreamSynchronize(s));
-  } catch (...) {
-    (void)hipStreamSynchronize(s);   // no in-flight DMA may outlive bp
-    bounce_release(bp);
-    throw;
+  for (uint64_t c = 0; c < nchunks; ++c) {
+    uint64_t coff = c * cs;
+    uint64_t clen = std::min<uint64_t>(cs, n - coff);
+    int slot = (int)(c & 1);
+    if (c >= 2) HIP_CHECK(hipEventSynchronize(l.bp->ev[slot]));
+    std::memcpy(l.bp->pin[slot], src + coff, clen);
+    HIP_CHECK(hipMemcpyAsync(dst + coff, l.bp->pin[slot], clen,
+                             hipMemcpyHostToDevice, l.s));
+    HIP_CHECK(hipEventRecord(l.bp->ev[slot], l.s));
   }
-  bounce_release(bp);
+  HIP_CHECK(hipStreamSynchronize(l.s));   // reports a failed copy; the lease
+                                          // only drains
 }
 
 static void arena_read(int h, uint64_t off, py::buffer buf, uint64_t buf_off,
@@ -575,8 +624,9 @@ static void arena_write(int h, uint64_t off, py::buffer buf, uint64_t buf_off,
 }
 
 // raw-pointer variants (torch tensors, pinned reply buffers, other arenas'
-// memory).  Uses the stream POOL: concurrent FUSE channel threads each get
-// their own stream, so large D2H copies overlap instead of serializing.
+// memory).  Copies ride the caller's thread_stream(device): concurrent FUSE
+// channel threads each have their own stream, so large D2H copies overlap
+// instead of serializing.
 static void arena_read_ptr(int h, uint64_t off, uintptr_t dst, uint64_t n,
                            bool dst_is_device) {
   Arena* a = get_arena(h);
@@ -647,6 +697,16 @@ static void arena_copy(int dst_h, uint64_t dst_off, int src_h, uint64_t src_off,
 
 // ---- kernels ----
 
+// every launch: clear the thread's stale last error, launch, and surface a
+// launch failure here instead of at some later call
+template <class... P, class... A>
+static void launch(void (*kernel)(P...), unsigned grid, unsigned block,
+                   hipStream_t s, A... args) {
+  (void)hipGetLastError();
+  hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), 0, s, args...);
+  HIP_CHECK(hipGetLastError());
+}
+
 static int grid_for(uint64_t work_items) {
   // >> 256 workgroups to fill 8 XCDs; cap for grid-stride loops
   uint64_t g = (work_items + WG - 1) / WG;
@@ -665,10 +725,8 @@ static void arena_fill(int h, uint64_t off, uint64_t n, int value) {
   }
   std::lock_guard<std::mutex> g(a->mu);
   HIP_CHECK(hipSetDevice(a->device));
-  (void)hipGetLastError();   // clear stale per-thread state
-  hipLaunchKernelGGL(fill_kernel, dim3(grid_for(n / 16 + 1)), dim3(WG), 0,
-                     a->kstream, (uint8_t*)a->base + off, (uint8_t)value, n);
-  HIP_CHECK(hipGetLastError());
+  launch(fill_kernel, grid_for(n / 16 + 1), WG, a->kstream,
+         (uint8_t*)a->base + off, (uint8_t)value, n);
   HIP_CHECK(hipStreamSynchronize(a->kstream));
 }
 
@@ -680,12 +738,9 @@ static uint32_t dev_crc32c_aligned(Arena* a, const uint8_t* p, uint64_t n) {
   uint32_t result = 0;
   if (n_sub) {
     uint32_t n_wg = (uint32_t)((n_sub + WG - 1) / WG);
-    ensure_scratch(a, n_wg * sizeof(uint32_t) + a->pin_sz);
-    uint32_t* d_out = (uint32_t*)a->scratch;
-    (void)hipGetLastError();   // clear stale per-thread state
-    hipLaunchKernelGGL(crc32c_kernel, dim3(n_wg), dim3(WG), 0, a->kstream, p,
-                       n_sub, d_out);
-    HIP_CHECK(hipGetLastError());
+    Scratch sc(a, n_wg * sizeof(uint32_t) + a->pin_sz);
+    uint32_t* d_out = sc.take<uint32_t>(n_wg);
+    launch(crc32c_kernel, n_wg, WG, a->kstream, p, n_sub, d_out);
     std::vector<uint32_t> host_out(n_wg);
     HIP_CHECK(hipMemcpyAsync(host_out.data(), d_out, n_wg * sizeof(uint32_t),
                              hipMemcpyDeviceToHost, a->kstream));
@@ -723,13 +778,12 @@ static uint32_t arena_crc32c(int h, uint64_t off, uint64_t n) {
   if (!a->is_dev()) {
     const uint8_t* p = (const uint8_t*)a->base + off;
     py::gil_scoped_release rel;
-    crc_init_tables();
     return crc32c_sw(p, n, 0);
   }
   py::gil_scoped_release rel;
   std::lock_guard<std::mutex> g(a->mu);
   HIP_CHECK(hipSetDevice(a->device));
-  ensure_crc_tables(a);
+  ensure_crc_tables(a->device);
   const uint8_t* p = (const uint8_t*)a->base + off;
   // any byte offset: the up-to-7 bytes before the next 8 B boundary are
   // read back and checksummed here, the aligned rest goes to the kernel
@@ -749,8 +803,85 @@ static uint32_t crc32c_buf(py::buffer buf, uint32_t init) {
   const uint8_t* p = (const uint8_t*)info.ptr;
   size_t n = (size_t)info.size * info.itemsize;
   py::gil_scoped_release rel;
-  crc_init_tables();
   return crc32c_sw(p, n, init);
+}
+
+// ---- tile tables ----
+//
+// The tiled kernels (copy_extents_kernel, convert_segments_kernel) take an
+// item table plus, per tile, the item it belongs to and its offset inside
+// that item, so one grid is load-balanced whatever the items' sizes.
+
+struct Tiles {
+  std::vector<uint32_t> item;
+  std::vector<uint64_t> off;
+  bool empty() const { return item.empty(); }
+  // scratch needed for `n_items` Items and up to `n_tiles` tiles
+  template <class Item> static size_t room(size_t n_items, size_t n_tiles) {
+    return Scratch::room<Item>(n_items) + Scratch::room<uint64_t>(n_tiles) +
+           Scratch::room<uint32_t>(n_tiles);
+  }
+  template <class Item> size_t room(size_t n_items) const {
+    return room<Item>(n_items, item.size());
+  }
+};
+
+// item i, len(i) units long, is cut into tiles of step(i) units
+template <class Len, class Step>
+static Tiles build_tiles(size_t n_items, Len len, Step step, const char* who) {
+  Tiles t;
+  for (size_t i = 0; i < n_items; ++i)
+    for (uint64_t o = 0, n = len(i), s = step(i); o < n; o += s) {
+      t.item.push_back((uint32_t)i);
+      t.off.push_back(o);
+    }
+  if (t.item.size() > 0xFFFFFFFFull)   // the kernels count tiles in uint32_t
+    throw std::invalid_argument(std::string(who) +
+                                ": too many tiles in one call");
+  return t;
+}
+
+template <class Item> struct DevTiles {
+  const Item* items;
+  const uint32_t* tile_item;
+  const uint64_t* tile_off;
+  uint32_t n_tiles;
+  unsigned grid() const { return std::min<uint32_t>(n_tiles, 8192); }
+};
+
+// carve the three tables (8-byte fields first) and upload them on kstream
+template <class Item>
+static DevTiles<Item> upload_tiles(Arena* a, Scratch& sc,
+                                   const std::vector<Item>& items,
+                                   const Tiles& t) {
+  Item* d_items = sc.take<Item>(items.size());
+  uint64_t* d_off = sc.take<uint64_t>(t.off.size());
+  uint32_t* d_item = sc.take<uint32_t>(t.item.size());
+  HIP_CHECK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(Item),
+                           hipMemcpyHostToDevice, a->kstream));
+  HIP_CHECK(hipMemcpyAsync(d_off, t.off.data(), t.off.size() * sizeof(uint64_t),
+                           hipMemcpyHostToDevice, a->kstream));
+  HIP_CHECK(hipMemcpyAsync(d_item, t.item.data(),
+                           t.item.size() * sizeof(uint32_t),
+                           hipMemcpyHostToDevice, a->kstream));
+  return {d_items, d_item, d_off, (uint32_t)t.item.size()};
+}
+
+static Tiles extent_tiles(const std::vector<Extent>& exts, const char* who) {
+  return build_tiles(exts.size(), [&](size_t i) { return exts[i].len; },
+                     [](size_t) { return (uint64_t)TILE; }, who);
+}
+
+// copy exts[i] = (src_off, dst_off, len) from src_base to dst_base on
+// kstream; `tiles` is extent_tiles(exts) and not empty, `sc` has
+// tiles.room<Extent>() left.  The caller syncs.
+static void launch_copy_extents(Arena* a, Scratch& sc, const uint8_t* src_base,
+                                uint8_t* dst_base,
+                                const std::vector<Extent>& exts,
+                                const Tiles& tiles) {
+  DevTiles<Extent> d = upload_tiles(a, sc, exts, tiles);
+  launch(copy_extents_kernel, d.grid(), WG, a->kstream, src_base, dst_base,
+         d.items, d.tile_item, d.tile_off, d.n_tiles);
 }
 
 // gather device extents into a host buffer: kernel packs extents into
@@ -775,43 +906,18 @@ static void arena_gather(int h, std::vector<std::pair<uint64_t, uint64_t>> ext,
   }
   std::lock_guard<std::mutex> g(a->mu);
   HIP_CHECK(hipSetDevice(a->device));
-  // build extent + tile tables
   std::vector<Extent> exts(ext.size());
-  std::vector<uint32_t> tile_ext;
-  std::vector<uint64_t> tile_off;
   uint64_t o = 0;
   for (size_t i = 0; i < ext.size(); ++i) {
     exts[i] = {ext[i].first, o, ext[i].second};
-    for (uint64_t t = 0; t < ext[i].second; t += TILE) {
-      tile_ext.push_back((uint32_t)i);
-      tile_off.push_back(t);
-    }
     o += ext[i].second;
   }
-  if (tile_ext.empty()) return;   // nothing to copy: no grid-0 launch
-  size_t meta = exts.size() * sizeof(Extent) +
-                tile_ext.size() * (sizeof(uint32_t) + sizeof(uint64_t));
-  // slack: up to 63 B to round `total` up to the extent table, up to 4 B
-  // to align the tile offsets
-  ensure_scratch(a, total + meta + 128);
-  uint8_t* d_pack = (uint8_t*)a->scratch;
-  Extent* d_ext = (Extent*)(d_pack + ((total + 63) & ~63ull));
-  uint32_t* d_te = (uint32_t*)(d_ext + exts.size());
-  uint64_t* d_to = (uint64_t*)(((uintptr_t)(d_te + tile_ext.size()) + 7) & ~7ull);
-  HIP_CHECK(hipMemcpyAsync(d_ext, exts.data(), exts.size() * sizeof(Extent),
-                           hipMemcpyHostToDevice, a->kstream));
-  HIP_CHECK(hipMemcpyAsync(d_te, tile_ext.data(),
-                           tile_ext.size() * sizeof(uint32_t),
-                           hipMemcpyHostToDevice, a->kstream));
-  HIP_CHECK(hipMemcpyAsync(d_to, tile_off.data(),
-                           tile_off.size() * sizeof(uint64_t),
-                           hipMemcpyHostToDevice, a->kstream));
-  int grid = (int)std::min<size_t>(tile_ext.size(), 8192);
-  (void)hipGetLastError();   // clear stale per-thread state
-  hipLaunchKernelGGL(copy_extents_kernel, dim3(grid), dim3(WG), 0, a->kstream,
-                     (const uint8_t*)a->base, d_pack, d_ext, d_te, d_to,
-                     (uint32_t)tile_ext.size());
-  HIP_CHECK(hipGetLastError());
+  Tiles tiles = extent_tiles(exts, "gather");
+  if (tiles.empty()) return;   // nothing to copy: no grid-0 launch
+  // the packed region sits at the scratch base, tables behind it
+  Scratch sc(a, Scratch::room<uint8_t>(total) + tiles.room<Extent>(exts.size()));
+  uint8_t* d_pack = sc.take<uint8_t>(total);
+  launch_copy_extents(a, sc, (const uint8_t*)a->base, d_pack, exts, tiles);
   HIP_CHECK(hipStreamSynchronize(a->kstream));
   // pipelined D2H of the packed region
   size_t nb = a->pin.size();
@@ -858,36 +964,12 @@ static void arena_gather_ptr(
   std::lock_guard<std::mutex> g(a->mu);
   HIP_CHECK(hipSetDevice(a->device));
   std::vector<Extent> exts(ext.size());
-  std::vector<uint32_t> tile_ext;
-  std::vector<uint64_t> tile_off;
-  for (size_t i = 0; i < ext.size(); ++i) {
+  for (size_t i = 0; i < ext.size(); ++i)
     exts[i] = {std::get<0>(ext[i]), std::get<1>(ext[i]), std::get<2>(ext[i])};
-    for (uint64_t t = 0; t < exts[i].len; t += TILE) {
-      tile_ext.push_back((uint32_t)i);
-      tile_off.push_back(t);
-    }
-  }
-  if (tile_ext.empty()) return;   // nothing to copy: no grid-0 launch
-  size_t meta = exts.size() * sizeof(Extent) +
-                tile_ext.size() * (sizeof(uint32_t) + sizeof(uint64_t)) + 64;
-  ensure_scratch(a, meta);
-  Extent* d_ext = (Extent*)a->scratch;
-  uint32_t* d_te = (uint32_t*)(d_ext + exts.size());
-  uint64_t* d_to = (uint64_t*)(((uintptr_t)(d_te + tile_ext.size()) + 7) & ~7ull);
-  HIP_CHECK(hipMemcpyAsync(d_ext, exts.data(), exts.size() * sizeof(Extent),
-                           hipMemcpyHostToDevice, a->kstream));
-  HIP_CHECK(hipMemcpyAsync(d_te, tile_ext.data(),
-                           tile_ext.size() * sizeof(uint32_t),
-                           hipMemcpyHostToDevice, a->kstream));
-  HIP_CHECK(hipMemcpyAsync(d_to, tile_off.data(),
-                           tile_off.size() * sizeof(uint64_t),
-                           hipMemcpyHostToDevice, a->kstream));
-  int grid = (int)std::min<size_t>(tile_ext.size(), 8192);
-  (void)hipGetLastError();   // clear stale per-thread state
-  hipLaunchKernelGGL(copy_extents_kernel, dim3(grid), dim3(WG), 0, a->kstream,
-                     (const uint8_t*)a->base, dst, d_ext, d_te, d_to,
-                     (uint32_t)tile_ext.size());
-  HIP_CHECK(hipGetLastError());
+  Tiles tiles = extent_tiles(exts, "gather");
+  if (tiles.empty()) return;   // nothing to copy: no grid-0 launch
+  Scratch sc(a, tiles.room<Extent>(exts.size()));
+  launch_copy_extents(a, sc, (const uint8_t*)a->base, dst, exts, tiles);
   HIP_CHECK(hipStreamSynchronize(a->kstream));
 }
 
@@ -949,40 +1031,16 @@ static void arena_convert_ptr(int h, std::vector<CastSegTuple> segs_in) {
     for (auto& g : segs) convert_segment_host((const uint8_t*)a->base, g);
     return;
   }
-  std::vector<uint32_t> tile_seg;
-  std::vector<uint64_t> tile_off;
-  for (size_t i = 0; i < segs.size(); ++i) {
-    uint64_t total = segs[i].rows * segs[i].run;
-    uint64_t step = cast_tile_elems(segs[i].src_dt, segs[i].dst_dt);
-    for (uint64_t t = 0; t < total; t += step) {
-      tile_seg.push_back((uint32_t)i);
-      tile_off.push_back(t);
-    }
-  }
-  if (tile_seg.size() > 0xFFFFFFFFull)
-    throw std::invalid_argument("convert: too many tiles in one call");
+  Tiles tiles = build_tiles(
+      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
+      [&](size_t i) { return cast_tile_elems(segs[i].src_dt, segs[i].dst_dt); },
+      "convert");
   std::lock_guard<std::mutex> g(a->mu);
   HIP_CHECK(hipSetDevice(a->device));
-  size_t seg_b = segs.size() * sizeof(CastSeg);
-  size_t off_b = tile_off.size() * sizeof(uint64_t);
-  size_t idx_b = tile_seg.size() * sizeof(uint32_t);
-  ensure_scratch(a, seg_b + off_b + idx_b + 64);
-  // 8-byte fields first so every table keeps its natural alignment
-  CastSeg* d_seg = (CastSeg*)a->scratch;
-  uint64_t* d_to = (uint64_t*)((uint8_t*)a->scratch + seg_b);
-  uint32_t* d_ts = (uint32_t*)((uint8_t*)a->scratch + seg_b + off_b);
-  HIP_CHECK(hipMemcpyAsync(d_seg, segs.data(), seg_b, hipMemcpyHostToDevice,
-                           a->kstream));
-  HIP_CHECK(hipMemcpyAsync(d_to, tile_off.data(), off_b, hipMemcpyHostToDevice,
-                           a->kstream));
-  HIP_CHECK(hipMemcpyAsync(d_ts, tile_seg.data(), idx_b, hipMemcpyHostToDevice,
-                           a->kstream));
-  int grid = (int)std::min<size_t>(tile_seg.size(), 8192);
-  (void)hipGetLastError();   // clear stale per-thread state
-  hipLaunchKernelGGL(convert_segments_kernel, dim3(grid), dim3(WG), 0,
-                     a->kstream, (const uint8_t*)a->base, d_seg, d_ts, d_to,
-                     (uint32_t)tile_seg.size());
-  HIP_CHECK(hipGetLastError());
+  Scratch sc(a, tiles.room<CastSeg>(segs.size()));
+  DevTiles<CastSeg> d = upload_tiles(a, sc, segs, tiles);
+  launch(convert_segments_kernel, d.grid(), WG, a->kstream,
+         (const uint8_t*)a->base, d.items, d.tile_item, d.tile_off, d.n_tiles);
   HIP_CHECK(hipStreamSynchronize(a->kstream));
 }
 
@@ -1140,34 +1198,49 @@ static py::list reader_pread_batch(int64_t rid,
 // decompress-into-arena (GPU)
 // ---------------------------------------------------------------------------
 
+// CVLZ: magic u32 | raw size u64 | chunk size u32 | n_chunks u32 |
+// sizes u32[n_chunks] | chunk payloads back to back
+static uint32_t lz4_chunk_count(uint64_t n) {
+  return (uint32_t)((n + LZ4_CHUNK - 1) / LZ4_CHUNK);
+}
+static size_t lz4_header_size(uint32_t n_chunks) { return 20 + 4ull * n_chunks; }
+
+static void lz4_write_header(uint8_t* h, uint64_t raw,
+                             const std::vector<uint32_t>& sizes) {
+  uint32_t ck = LZ4_CHUNK, n_chunks = (uint32_t)sizes.size();
+  memcpy(h, &LZ4_MAGIC, 4);
+  memcpy(h + 4, &raw, 8);
+  memcpy(h + 12, &ck, 4);
+  memcpy(h + 16, &n_chunks, 4);
+  memcpy(h + 20, sizes.data(), 4ull * n_chunks);
+}
+
+// host codec: compress src[0, n) chunk by chunk, appending the payloads to
+// `out` and recording sizes[c]
+static void lz4_compress_host(const uint8_t* src, size_t n,
+                              std::vector<uint32_t>& sizes,
+                              std::vector<uint8_t>& out) {
+  std::vector<uint8_t> tmp(LZ4_CHUNK + LZ4_CHUNK / 128 + 64);
+  for (size_t c = 0; c < sizes.size(); ++c) {
+    size_t cn = std::min<size_t>(LZ4_CHUNK, n - c * LZ4_CHUNK);
+    size_t cs = lz4_compress_block(src + c * LZ4_CHUNK, cn, tmp.data());
+    sizes[c] = (uint32_t)cs;
+    out.insert(out.end(), tmp.data(), tmp.data() + cs);
+  }
+}
+
 static py::bytes lz4_compress_py(py::buffer buf) {
   py::buffer_info info = buf.request(false);
   const uint8_t* src = (const uint8_t*)info.ptr;
   size_t n = (size_t)info.size * info.itemsize;
-  uint32_t n_chunks = (uint32_t)((n + LZ4_CHUNK - 1) / LZ4_CHUNK);
-  std::vector<uint32_t> sizes(n_chunks);
+  std::vector<uint32_t> sizes(lz4_chunk_count(n));
   std::vector<uint8_t> out;
   out.reserve(n / 2 + 1024);
-  size_t header = 4 + 8 + 4 + 4 + 4ull * n_chunks;
-  out.resize(header);
+  out.resize(lz4_header_size(sizes.size()));
   {
     py::gil_scoped_release rel;
-    std::vector<uint8_t> tmp(LZ4_CHUNK + LZ4_CHUNK / 128 + 64);
-    for (uint32_t c = 0; c < n_chunks; ++c) {
-      size_t cn = std::min<size_t>(LZ4_CHUNK, n - (size_t)c * LZ4_CHUNK);
-      size_t cs = lz4_compress_block(src + (size_t)c * LZ4_CHUNK, cn,
-                                     tmp.data());
-      sizes[c] = (uint32_t)cs;
-      out.insert(out.end(), tmp.data(), tmp.data() + cs);
-    }
-    uint8_t* h = out.data();
-    memcpy(h, &LZ4_MAGIC, 4);
-    uint64_t raw = n;
-    memcpy(h + 4, &raw, 8);
-    uint32_t ck = LZ4_CHUNK;
-    memcpy(h + 12, &ck, 4);
-    memcpy(h + 16, &n_chunks, 4);
-    memcpy(h + 20, sizes.data(), 4ull * n_chunks);
+    lz4_compress_host(src, n, sizes, out);
+    lz4_write_header(out.data(), n, sizes);
   }
   return py::bytes((const char*)out.data(), out.size());
 }
@@ -1203,6 +1276,18 @@ static Lz4Header lz4_parse(const uint8_t* p, size_t n) {
   return h;
 }
 
+// host codec: decompress a parsed container into dst[0, raw_size)
+static void lz4_decompress_host(const Lz4Header& h, uint8_t* dst) {
+  const uint8_t* p = h.payload;
+  for (uint32_t c = 0; c < h.n_chunks; ++c) {
+    uint64_t at = (uint64_t)c * h.chunk_size;
+    size_t cap = std::min<uint64_t>(h.chunk_size, h.raw_size - at);
+    size_t got = lz4_decompress_block_host(p, h.sizes[c], dst + at, cap);
+    if (got != cap) throw std::runtime_error("lz4: corrupt chunk");
+    p += h.sizes[c];
+  }
+}
+
 static py::bytes lz4_decompress_py(py::buffer buf) {
   py::buffer_info info = buf.request(false);
   const uint8_t* src = (const uint8_t*)info.ptr;
@@ -1211,16 +1296,7 @@ static py::bytes lz4_decompress_py(py::buffer buf) {
   std::string out(h.raw_size, '\0');
   {
     py::gil_scoped_release rel;
-    const uint8_t* p = h.payload;
-    for (uint32_t c = 0; c < h.n_chunks; ++c) {
-      size_t cap = std::min<uint64_t>(h.chunk_size,
-                                      h.raw_size - (uint64_t)c * h.chunk_size);
-      size_t got = lz4_decompress_block_host(
-          p, h.sizes[c], (uint8_t*)out.data() + (uint64_t)c * h.chunk_size,
-          cap);
-      if (got != cap) throw std::runtime_error("lz4: corrupt chunk");
-      p += h.sizes[c];
-    }
+    lz4_decompress_host(h, (uint8_t*)out.data());
   }
   return py::bytes(out);
 }
@@ -1237,16 +1313,7 @@ static uint64_t arena_lz4_decompress(int ah, uint64_t dst_off, py::buffer buf) {
   if (h.n_chunks == 0) return 0;   // empty container: no grid-0 launch
   py::gil_scoped_release rel;
   if (!a->is_dev()) {
-    const uint8_t* p = h.payload;
-    for (uint32_t c = 0; c < h.n_chunks; ++c) {
-      size_t cap = std::min<uint64_t>(h.chunk_size,
-                                      h.raw_size - (uint64_t)c * h.chunk_size);
-      size_t got = lz4_decompress_block_host(
-          p, h.sizes[c],
-          (uint8_t*)a->base + dst_off + (uint64_t)c * h.chunk_size, cap);
-      if (got != cap) throw std::runtime_error("lz4: corrupt chunk");
-      p += h.sizes[c];
-    }
+    lz4_decompress_host(h, (uint8_t*)a->base + dst_off);
     return h.raw_size;
   }
   std::lock_guard<std::mutex> g(a->mu);
@@ -1258,12 +1325,12 @@ static uint64_t arena_lz4_decompress(int ah, uint64_t dst_off, py::buffer buf) {
     acc += h.sizes[c];
   }
   size_t payload_n = acc;
-  size_t meta = 8ull * h.n_chunks + 64;
-  ensure_scratch(a, payload_n + meta + 64);
-  uint8_t* d_comp = (uint8_t*)a->scratch;
-  uint32_t* d_off = (uint32_t*)(d_comp + ((payload_n + 63) & ~63ull));
-  uint32_t* d_len = d_off + h.n_chunks;
-  int* d_err = (int*)(d_len + h.n_chunks);
+  Scratch sc(a, Scratch::room<uint8_t>(payload_n) +
+                    Scratch::room<uint32_t>(2ull * h.n_chunks + 1));
+  uint8_t* d_comp = sc.take<uint8_t>(payload_n);
+  uint32_t* d_off = sc.take<uint32_t>(h.n_chunks);
+  uint32_t* d_len = sc.take<uint32_t>(h.n_chunks);
+  int* d_err = (int*)sc.take<uint32_t>(1);
   HIP_CHECK(hipMemcpyAsync(d_comp, h.payload, payload_n,
                            hipMemcpyHostToDevice, a->kstream));
   HIP_CHECK(hipMemcpyAsync(d_off, offs.data(), 4ull * h.n_chunks,
@@ -1271,13 +1338,9 @@ static uint64_t arena_lz4_decompress(int ah, uint64_t dst_off, py::buffer buf) {
   HIP_CHECK(hipMemcpyAsync(d_len, h.sizes, 4ull * h.n_chunks,
                            hipMemcpyHostToDevice, a->kstream));
   HIP_CHECK(hipMemsetAsync(d_err, 0, 4, a->kstream));
-  int grid = (int)std::min<uint32_t>(h.n_chunks, 16384);
-  (void)hipGetLastError();   // clear stale per-thread state
-  hipLaunchKernelGGL(lz4_decompress_kernel, dim3(grid), dim3(64), 0,
-                     a->kstream, d_comp, d_off, d_len,
-                     (uint8_t*)a->base + dst_off, h.chunk_size, h.raw_size,
-                     h.n_chunks, d_err);
-  HIP_CHECK(hipGetLastError());
+  launch(lz4_decompress_kernel, std::min<uint32_t>(h.n_chunks, 16384), 64,
+         a->kstream, d_comp, d_off, d_len, (uint8_t*)a->base + dst_off,
+         h.chunk_size, h.raw_size, h.n_chunks, d_err);
   int err_host = 0;
   HIP_CHECK(hipMemcpyAsync(&err_host, d_err, 4, hipMemcpyDeviceToHost,
                            a->kstream));
@@ -1299,46 +1362,32 @@ static py::bytes arena_lz4_compress(int ah, uint64_t off, uint64_t n) {
     throw std::runtime_error(
         "lz4: compress of " + std::to_string(n) + " bytes exceeds the " +
         std::to_string(LZ4_DEVICE_MAX_N) + "-byte per-call limit; segment it");
-  uint32_t n_chunks = (uint32_t)((n + LZ4_CHUNK - 1) / LZ4_CHUNK);
-  size_t header = 20 + 4ull * n_chunks;
+  uint32_t n_chunks = lz4_chunk_count(n);
+  size_t header = lz4_header_size(n_chunks);
   std::vector<uint32_t> sizes(n_chunks);
   std::vector<uint8_t> out(header);
   {
     py::gil_scoped_release rel;
     if (!a->is_dev()) {
-      std::vector<uint8_t> tmp(LZ4_SLOT_STRIDE);
-      const uint8_t* src = (const uint8_t*)a->base + off;
-      for (uint32_t c = 0; c < n_chunks; ++c) {
-        size_t cn = std::min<size_t>(LZ4_CHUNK, n - (size_t)c * LZ4_CHUNK);
-        size_t cs = lz4_compress_block(src + (size_t)c * LZ4_CHUNK, cn,
-                                       tmp.data());
-        sizes[c] = (uint32_t)cs;
-        out.insert(out.end(), tmp.data(), tmp.data() + cs);
-      }
+      lz4_compress_host((const uint8_t*)a->base + off, n, sizes, out);
     } else if (n_chunks) {
       std::lock_guard<std::mutex> g(a->mu);
       HIP_CHECK(hipSetDevice(a->device));
-      // scratch: slots | packed payload | lens | err | extent + tile tables
+      // scratch: slots | packed payload | lens + err | extent + tile tables
+      // (a slot spans at most 2 tiles); the slot stride is a multiple of
+      // 64, so both byte regions start where they always did
       size_t slots_n = (size_t)n_chunks * LZ4_SLOT_STRIDE;
-      size_t max_tiles = 2ull * n_chunks;   // a slot spans at most 2 tiles
-      size_t meta = 4ull * n_chunks + 64 + n_chunks * sizeof(Extent) +
-                    max_tiles * (sizeof(uint32_t) + sizeof(uint64_t)) + 64;
-      ensure_scratch(a, 2 * slots_n + meta);
-      uint8_t* d_slots = (uint8_t*)a->scratch;
-      uint8_t* d_pack = d_slots + slots_n;
-      uint32_t* d_len = (uint32_t*)(d_pack + slots_n);
+      Scratch sc(a, 2 * Scratch::room<uint8_t>(slots_n) +
+                        Scratch::room<uint32_t>(n_chunks + 1) +
+                        Tiles::room<Extent>(n_chunks, 2ull * n_chunks));
+      uint8_t* d_slots = sc.take<uint8_t>(slots_n);
+      uint8_t* d_pack = sc.take<uint8_t>(slots_n);
+      uint32_t* d_len = sc.take<uint32_t>(n_chunks + 1);
       int* d_err = (int*)(d_len + n_chunks);
-      Extent* d_ext = (Extent*)(((uintptr_t)(d_err + 1) + 63) & ~63ull);
-      uint32_t* d_te = (uint32_t*)(d_ext + n_chunks);
-      uint64_t* d_to = (uint64_t*)(((uintptr_t)(d_te + max_tiles) + 7) & ~7ull);
       HIP_CHECK(hipMemsetAsync(d_err, 0, 4, a->kstream));
-      int grid = (int)std::min<uint32_t>(n_chunks, 16384);
-      (void)hipGetLastError();   // clear stale per-thread state
-      hipLaunchKernelGGL(lz4_compress_kernel, dim3(grid), dim3(64), 0,
-                         a->kstream, (const uint8_t*)a->base, off, n,
-                         (uint32_t)LZ4_CHUNK, d_slots, LZ4_SLOT_STRIDE, d_len,
-                         n_chunks, d_err);
-      HIP_CHECK(hipGetLastError());
+      launch(lz4_compress_kernel, std::min<uint32_t>(n_chunks, 16384), 64,
+             a->kstream, (const uint8_t*)a->base, off, n, (uint32_t)LZ4_CHUNK,
+             d_slots, LZ4_SLOT_STRIDE, d_len, n_chunks, d_err);
       // lens + error flag are adjacent: one small D2H
       std::vector<uint32_t> lens(n_chunks + 1);
       HIP_CHECK(hipMemcpyAsync(lens.data(), d_len, 4ull * (n_chunks + 1),
@@ -1348,45 +1397,22 @@ static py::bytes arena_lz4_compress(int ah, uint64_t off, uint64_t n) {
           "lz4: compress slot overflow in chunk " +
           std::to_string(lens[n_chunks] - 1) + " (device)");
       std::vector<Extent> exts(n_chunks);
-      std::vector<uint32_t> tile_ext;
-      std::vector<uint64_t> tile_off;
       uint64_t total = 0;
       for (uint32_t c = 0; c < n_chunks; ++c) {
         if (lens[c] == 0 || lens[c] > LZ4_SLOT_STRIDE)
           throw std::runtime_error("lz4: bad device chunk length");
         sizes[c] = lens[c];
         exts[c] = {(uint64_t)c * LZ4_SLOT_STRIDE, total, lens[c]};
-        for (uint64_t t = 0; t < lens[c]; t += TILE) {
-          tile_ext.push_back(c);
-          tile_off.push_back(t);
-        }
         total += lens[c];
       }
-      HIP_CHECK(hipMemcpyAsync(d_ext, exts.data(), exts.size() * sizeof(Extent),
-                               hipMemcpyHostToDevice, a->kstream));
-      HIP_CHECK(hipMemcpyAsync(d_te, tile_ext.data(),
-                               tile_ext.size() * sizeof(uint32_t),
-                               hipMemcpyHostToDevice, a->kstream));
-      HIP_CHECK(hipMemcpyAsync(d_to, tile_off.data(),
-                               tile_off.size() * sizeof(uint64_t),
-                               hipMemcpyHostToDevice, a->kstream));
-      hipLaunchKernelGGL(copy_extents_kernel,
-                         dim3((int)std::min<size_t>(tile_ext.size(), 8192)),
-                         dim3(WG), 0, a->kstream, (const uint8_t*)d_slots,
-                         d_pack, d_ext, d_te, d_to, (uint32_t)tile_ext.size());
-      HIP_CHECK(hipGetLastError());
+      launch_copy_extents(a, sc, d_slots, d_pack, exts,
+                          extent_tiles(exts, "lz4"));
       out.resize(header + total);
       HIP_CHECK(hipMemcpyAsync(out.data() + header, d_pack, total,
                                hipMemcpyDeviceToHost, a->kstream));
       HIP_CHECK(hipStreamSynchronize(a->kstream));
     }
-    uint8_t* h = out.data();
-    memcpy(h, &LZ4_MAGIC, 4);
-    memcpy(h + 4, &n, 8);
-    uint32_t ck = LZ4_CHUNK;
-    memcpy(h + 12, &ck, 4);
-    memcpy(h + 16, &n_chunks, 4);
-    memcpy(h + 20, sizes.data(), 4ull * n_chunks);
+    lz4_write_header(out.data(), n, sizes);
   }
   return py::bytes((const char*)out.data(), out.size());
 }

@@ -18,29 +18,19 @@ import threading
 
 _REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 _SO = os.path.join(_REPO, "curvine_amd", "_native.so")
-_SRC = os.path.join(_REPO, "csrc", "module.cpp")
-_SRC2 = os.path.join(_REPO, "csrc", "kernels.hip")
-_SRC3 = os.path.join(_REPO, "csrc", "lz4.hip")
-_SRC4 = os.path.join(_REPO, "csrc", "fuse_loop.hip")
-_SRC5 = os.path.join(_REPO, "csrc", "meta_server.cpp")
-_SRC6 = os.path.join(_REPO, "csrc", "data_server.cpp")
-_SRC7 = os.path.join(_REPO, "csrc", "sdk_abi.cpp")
-_SRC8 = os.path.join(_REPO, "csrc", "tensor_cast.hip")
+_CSRC = os.path.join(_REPO, "csrc")
+_SRC = os.path.join(_CSRC, "module.cpp")   # includes every other file there
 _lock = threading.Lock()
 _mod = None
 
 
 def build_native(force: bool = False) -> str:
-    """Compile csrc/ into curvine_amd/_native.so for gfx950."""
+    """Compile csrc/ into curvine_amd/_native.so for gfx950.  The .so is
+    stale when any csrc/*.cpp or csrc/*.hip is newer than it."""
     if not force and os.path.exists(_SO) and os.path.exists(_SRC):
-        if os.path.getmtime(_SO) >= max(os.path.getmtime(_SRC),
-                                        os.path.getmtime(_SRC2),
-                                        os.path.getmtime(_SRC3),
-                                        os.path.getmtime(_SRC4),
-                                        os.path.getmtime(_SRC5),
-                                        os.path.getmtime(_SRC6),
-                                        os.path.getmtime(_SRC7),
-                                        os.path.getmtime(_SRC8)):
+        sources = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC)
+                   if f.endswith((".cpp", ".hip"))]
+        if os.path.getmtime(_SO) >= max(map(os.path.getmtime, sources)):
             return _SO
     import pybind11
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
