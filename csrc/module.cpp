@@ -1062,6 +1062,117 @@ static py::bytes convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
   return py::bytes((const char*)out.data(), out_b);
 }
 
+// ---- typed tensor store (tensor_cast.hip) ----
+//
+// Segments: (src_ptr, dst_off, rows, run, src_pitch, src_dtype, dst_dtype):
+// the scatter direction of convert.  The source is an absolute address
+// (a torch tensor or a row-strided view of one), the destination dense at
+// dst_off.  Every argument error is raised here, before any launch.
+
+static CastSeg store_validate(uint64_t cap, uint64_t src_ptr, uint64_t dst_off,
+                              uint64_t rows, uint64_t run, uint64_t pitch,
+                              uint64_t sdt, uint64_t ddt) {
+  if (sdt >= DT_COUNT || ddt >= DT_COUNT)
+    throw std::invalid_argument("store: unknown dtype code");
+  if (sdt != ddt && !cast_pair_converts((uint32_t)sdt, (uint32_t)ddt))
+    throw std::invalid_argument("store: unsupported dtype pair");
+  uint64_t ss = cast_itemsize((uint32_t)sdt), ds = cast_itemsize((uint32_t)ddt);
+  uint64_t run_b, span, end, total, dst_b;
+  if (__builtin_mul_overflow(run, ss, &run_b) ||
+      __builtin_mul_overflow(rows, run, &total) ||
+      __builtin_mul_overflow(total, ds, &dst_b) ||
+      __builtin_add_overflow(dst_off, dst_b, &end))
+    throw std::invalid_argument("store: segment size overflows");
+  if (end > cap) throw std::invalid_argument("store: arena range out of bounds");
+  if (total) {
+    // last source byte: src_ptr + (rows-1)*pitch + run*ss, overflow-checked
+    if (__builtin_mul_overflow(rows - 1, pitch, &span) ||
+        __builtin_add_overflow(span, run_b, &span) ||
+        __builtin_add_overflow(src_ptr, span, &end))
+      throw std::invalid_argument("store: source range overflows");
+    if (src_ptr == 0 || src_ptr % ss)
+      throw std::invalid_argument("store: src_ptr null or misaligned");
+    if (dst_off % ds)
+      throw std::invalid_argument("store: dst_off misaligned");
+  }
+  CastSeg g;
+  g.src_off = src_ptr; g.dst_ptr = dst_off; g.rows = rows; g.run = run;
+  g.src_pitch = pitch; g.src_dt = (uint32_t)sdt; g.dst_dt = (uint32_t)ddt;
+  if (sdt == ddt) {            // raw copy at any itemsize: flatten to bytes
+    g.run = run_b;
+    g.src_dt = g.dst_dt = DT_U8;
+  }
+  return g;
+}
+
+// a device arena's kernel dereferences the source: it has to be memory of
+// the arena's own GPU (or pinned host memory), and where the runtime knows
+// the allocation's extent the segment has to lie inside it.  `known` holds
+// the allocations already checked in this call: the tensors of a checkpoint
+// mostly share a few allocator blocks, and the runtime queries cost more
+// than the rest of a small call.  Caller has set the device.
+static void store_check_source(
+    Arena* a, const CastSeg& g,
+    std::vector<std::pair<uint64_t, uint64_t>>& known) {
+  uint64_t first = g.src_off;
+  uint64_t last = first + (g.rows - 1) * g.src_pitch +
+                  g.run * cast_itemsize(g.src_dt);   // validated: no overflow
+  for (auto& k : known)
+    if (first >= k.first && last <= k.second) return;
+  hipPointerAttribute_t at;
+  const void* p = (const void*)(uintptr_t)first;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    throw std::invalid_argument("store: src_ptr is not device-visible memory");
+  }
+  if (at.type == hipMemoryTypeDevice && at.device != a->device)
+    throw std::invalid_argument("store: source lives on another device");
+  if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost &&
+      at.type != hipMemoryTypeManaged)
+    throw std::invalid_argument("store: src_ptr is not device-visible memory");
+  hipDeviceptr_t lo;
+  size_t sz;
+  if (hipMemGetAddressRange(&lo, &sz, (hipDeviceptr_t)p) != hipSuccess) {
+    (void)hipGetLastError();   // extent unknown to the runtime: type check only
+    return;
+  }
+  if (last > (uint64_t)(uintptr_t)lo + sz)
+    throw std::invalid_argument("store: source runs past its allocation");
+  known.emplace_back((uint64_t)(uintptr_t)lo, (uint64_t)(uintptr_t)lo + sz);
+}
+
+static void arena_store_ptr(int h, std::vector<CastSegTuple> segs_in) {
+  Arena* a = get_arena(h);
+  std::vector<CastSeg> segs;
+  segs.reserve(segs_in.size());
+  for (auto& t : segs_in) {
+    CastSeg g = store_validate(a->cap, std::get<0>(t), std::get<1>(t),
+                               std::get<2>(t), std::get<3>(t), std::get<4>(t),
+                               std::get<5>(t), std::get<6>(t));
+    if (g.rows * g.run) segs.push_back(g);
+  }
+  if (segs.empty()) return;
+  py::gil_scoped_release rel;
+  if (!a->is_dev()) {
+    for (auto& g : segs) store_segment_host((uint8_t*)a->base, g);
+    return;
+  }
+  Tiles tiles = build_tiles(
+      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
+      [&](size_t i) { return cast_tile_elems(segs[i].src_dt, segs[i].dst_dt); },
+      "store");
+  std::lock_guard<std::mutex> g(a->mu);
+  HIP_CHECK(hipSetDevice(a->device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  for (auto& s : segs) store_check_source(a, s, known);
+  Scratch sc(a, tiles.room<CastSeg>(segs.size()));
+  DevTiles<CastSeg> d = upload_tiles(a, sc, segs, tiles);
+  launch(store_segments_kernel, d.grid(), WG, a->kstream,
+         (uint8_t*)a->base, d.items, d.tile_item, d.tile_off, d.n_tiles);
+  // the sources are the caller's to free or overwrite once this returns
+  HIP_CHECK(hipStreamSynchronize(a->kstream));
+}
+
 static uintptr_t arena_base_ptr(int h) {
   return (uintptr_t)get_arena(h)->base;
 }
@@ -1591,6 +1702,7 @@ PYBIND11_MODULE(_native, m) {
   m.def("arena_gather", &arena_gather);
   m.def("arena_gather_ptr", &arena_gather_ptr);
   m.def("arena_convert_ptr", &arena_convert_ptr);
+  m.def("arena_store_ptr", &arena_store_ptr);
   m.def("convert_host", &convert_host);
   m.def("arena_base_ptr", &arena_base_ptr);
   m.def("arena_read_batch", &arena_read_batch);

@@ -1,12 +1,17 @@
-// Typed tensor load for curvine_amd: arena bytes -> dtype-converted,
-// optionally strided, dense destination (safetensors weights living in the
-// HBM cache land in torch parameters in one pass).
+// Typed tensor load and store for curvine_amd: optionally strided source ->
+// dtype-converted dense destination.  Load (convert_segments_kernel): arena
+// bytes -> torch tensor, safetensors weights living in the HBM cache land
+// in torch parameters in one pass.  Store (store_segments_kernel): torch
+// tensor or row-strided view -> arena bytes, a checkpoint's data section is
+// written where it will be cached, with no host hop.
 //
 // One segment = `rows` runs of `run` contiguous source elements, the runs
-// `src_pitch` bytes apart in the arena, written densely at `dst_ptr`.  The
+// `src_pitch` bytes apart, written densely at the destination.  A load's
 // source may sit at ANY byte alignment (the safetensors data section starts
-// wherever the JSON header ends); the destination is aligned to its own
-// itemsize (torch allocations) but run boundaries inside it are not.
+// wherever the JSON header ends); a store's source is aligned to its own
+// itemsize only (views with a storage offset, run starts inside a strided
+// tensor).  The destination is aligned to its own itemsize but run
+// boundaries inside it are not.
 //
 // Numerics: integer bit manipulation only, shared by the kernel and the
 // host loop (`__host__ __device__`), bitwise equal to torch's CPU `.to()`:
@@ -138,8 +143,10 @@ __host__ __device__ inline void cast_one(const uint8_t* s, uint8_t* d,
 // ---------------------------------------------------------------------------
 
 struct CastSeg {
-  uint64_t src_off;     // bytes into the arena, any alignment
-  uint64_t dst_ptr;     // absolute address of dense element 0
+  uint64_t src_off;     // load: bytes into the arena, any alignment;
+                        // store: absolute source address of row 0
+  uint64_t dst_ptr;     // load: absolute address of dense element 0;
+                        // store: bytes into the arena
   uint64_t rows, run;   // rows runs of run elements
   uint64_t src_pitch;   // bytes between run starts in the source
   uint32_t src_dt, dst_dt;
@@ -156,8 +163,12 @@ __host__ __device__ inline uint64_t cast_tile_elems(uint32_t sdt, uint32_t ddt) 
 
 // load W dwords of source for one unit. mode 0: natural vector alignment,
 // 1: 4-byte aligned, 2: unaligned (aligned dwords + byte funnel shift; reads
-// up to 3 bytes before p and up to 4 bytes past the unit, which the caller
-// guarantees to lie inside the run's source bytes or the arena's first word)
+// the aligned dword that holds p's byte, so up to 3 bytes before p, and up
+// to 3 bytes past the unit).  Guarantee of cast_run, which holds for an
+// absolute source (a torch tensor) as for an arena offset: before a run at
+// most the aligned dword that holds the run's first byte is touched, which
+// lies in the same allocation and page as that byte; past the run's last
+// byte nothing is touched.
 template <int W>
 __device__ __forceinline__ void cast_load_words(const uint8_t* p, int mode,
                                                 uint32_t (&w)[W]) {
@@ -223,8 +234,9 @@ __device__ __forceinline__ void cast_run(const uint8_t* s, uint8_t* d,
   const uint8_t* sb = s + hd * SS;
   int mode = ((uintptr_t)sb & (W * 4 - 1)) == 0 ? 0
              : (((uintptr_t)sb & 3) == 0 ? 1 : 2);
-  // the shifted loads over-read past their unit: keep the last unit out of
-  // the body so the over-read stays inside this run's own source bytes
+  // the shifted loads over-read up to 3 bytes past their unit: keep the
+  // last unit out of the body, so those bytes belong to the unit after it
+  // and nothing past the run's last byte is read
   if (mode == 2 && nb > 0) nb--;
   uint64_t tail0 = hd + nb * K;
 
@@ -256,14 +268,12 @@ __device__ __forceinline__ void cast_run(const uint8_t* s, uint8_t* d,
 }
 
 template <uint32_t SDT, uint32_t DDT>
-__device__ __forceinline__ void cast_tile(const uint8_t* base,
+__device__ __forceinline__ void cast_tile(const uint8_t* src, uint8_t* dst,
                                           const CastSeg& g, uint64_t t0,
                                           uint64_t t1) {
   constexpr bool COPY = (SDT == DDT);
   constexpr uint32_t SS = COPY ? 1 : (SDT == DT_F32 ? 4 : (SDT <= DT_BF16 ? 2 : 1));
   constexpr uint32_t DS = COPY ? 1 : (DDT == DT_F32 ? 4 : 2);
-  const uint8_t* src = base + g.src_off;
-  uint8_t* dst = reinterpret_cast<uint8_t*>(g.dst_ptr);
   if (g.run >= CAST_SHORT_RUN) {
     uint64_t e = t0;
     while (e < t1) {                       // workgroup-uniform loop
@@ -285,39 +295,57 @@ __device__ __forceinline__ void cast_tile(const uint8_t* base,
 
 // Tile table as in copy_extents_kernel: tile -> segment, tile -> first dense
 // element; grid-stride over tiles so one huge embedding and 300
-// norm vectors in the same call spread evenly over the CUs.
+// norm vectors in the same call spread evenly over the CUs.  `src` and
+// `dst` are the segment's row 0 and dense element 0.
+__device__ __forceinline__ void cast_segment_tiles(
+    const uint8_t* src, uint8_t* dst, const CastSeg& g, uint64_t t0) {
+  uint64_t t1 = min(t0 + cast_tile_elems(g.src_dt, g.dst_dt), g.rows * g.run);
+#define CAST_CASE(S, D) \
+  case (S) * 16u + (D): cast_tile<S, D>(src, dst, g, t0, t1); break;
+  switch (g.src_dt * 16u + g.dst_dt) {
+    CAST_CASE(DT_U8, DT_U8)
+    CAST_CASE(DT_F32, DT_F16) CAST_CASE(DT_F32, DT_BF16)
+    CAST_CASE(DT_F16, DT_F32) CAST_CASE(DT_F16, DT_BF16)
+    CAST_CASE(DT_BF16, DT_F32) CAST_CASE(DT_BF16, DT_F16)
+    CAST_CASE(DT_F8_E4M3, DT_F32) CAST_CASE(DT_F8_E4M3, DT_F16)
+    CAST_CASE(DT_F8_E4M3, DT_BF16)
+    CAST_CASE(DT_F8_E5M2, DT_F32) CAST_CASE(DT_F8_E5M2, DT_F16)
+    CAST_CASE(DT_F8_E5M2, DT_BF16)
+    default: break;   // host rejects every other pair before launch
+  }
+#undef CAST_CASE
+}
+
 extern "C" __global__ __launch_bounds__(WG) void convert_segments_kernel(
     const uint8_t* __restrict__ base, const CastSeg* __restrict__ segs,
     const uint32_t* __restrict__ tile_seg, const uint64_t* __restrict__ tile_off,
     uint32_t n_tiles) {
   for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     CastSeg g = segs[tile_seg[tile]];
-    uint64_t t0 = tile_off[tile];
-    uint64_t t1 = min(t0 + cast_tile_elems(g.src_dt, g.dst_dt),
-                      g.rows * g.run);
-#define CAST_CASE(S, D) \
-    case (S) * 16u + (D): cast_tile<S, D>(base, g, t0, t1); break;
-    switch (g.src_dt * 16u + g.dst_dt) {
-      CAST_CASE(DT_U8, DT_U8)
-      CAST_CASE(DT_F32, DT_F16) CAST_CASE(DT_F32, DT_BF16)
-      CAST_CASE(DT_F16, DT_F32) CAST_CASE(DT_F16, DT_BF16)
-      CAST_CASE(DT_BF16, DT_F32) CAST_CASE(DT_BF16, DT_F16)
-      CAST_CASE(DT_F8_E4M3, DT_F32) CAST_CASE(DT_F8_E4M3, DT_F16)
-      CAST_CASE(DT_F8_E4M3, DT_BF16)
-      CAST_CASE(DT_F8_E5M2, DT_F32) CAST_CASE(DT_F8_E5M2, DT_F16)
-      CAST_CASE(DT_F8_E5M2, DT_BF16)
-      default: break;   // host rejects every other pair before launch
-    }
-#undef CAST_CASE
+    cast_segment_tiles(base + g.src_off, reinterpret_cast<uint8_t*>(g.dst_ptr),
+                       g, tile_off[tile]);
+  }
+}
+
+// The scatter direction: absolute sources (src_off holds the address),
+// dense destinations at dst_ptr bytes into the arena at `base`.
+extern "C" __global__ __launch_bounds__(WG) void store_segments_kernel(
+    uint8_t* __restrict__ base, const CastSeg* __restrict__ segs,
+    const uint32_t* __restrict__ tile_seg, const uint64_t* __restrict__ tile_off,
+    uint32_t n_tiles) {
+  for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    CastSeg g = segs[tile_seg[tile]];
+    cast_segment_tiles(reinterpret_cast<const uint8_t*>(g.src_off),
+                       base + g.dst_ptr, g, tile_off[tile]);
   }
 }
 
 // host arena: the same segments, the same scalar routines, plain loops
-static void convert_segment_host(const uint8_t* base, const CastSeg& g) {
+static void cast_segment_host(const uint8_t* src, uint8_t* dst,
+                              const CastSeg& g) {
   uint32_t ss = cast_itemsize(g.src_dt), ds = cast_itemsize(g.dst_dt);
-  uint8_t* dst = reinterpret_cast<uint8_t*>(g.dst_ptr);
   for (uint64_t r = 0; r < g.rows; ++r) {
-    const uint8_t* s = base + g.src_off + r * g.src_pitch;
+    const uint8_t* s = src + r * g.src_pitch;
     uint8_t* d = dst + r * g.run * ds;
     if (g.src_dt == g.dst_dt) {
       std::memcpy(d, s, g.run * ss);
@@ -326,4 +354,14 @@ static void convert_segment_host(const uint8_t* base, const CastSeg& g) {
     for (uint64_t c = 0; c < g.run; ++c)
       cast_one(s + c * ss, d + c * ds, g.src_dt, g.dst_dt);
   }
+}
+
+static void convert_segment_host(const uint8_t* base, const CastSeg& g) {
+  cast_segment_host(base + g.src_off, reinterpret_cast<uint8_t*>(g.dst_ptr), g);
+}
+
+// host arena, CPU source: src_off is the absolute source address
+static void store_segment_host(uint8_t* base, const CastSeg& g) {
+  cast_segment_host(reinterpret_cast<const uint8_t*>(g.src_off),
+                    base + g.dst_ptr, g);
 }

@@ -166,6 +166,22 @@ class CurvineFileSystem:
         await w.write(data)
         return await w.complete()
 
+    async def write_typed(self, path: str, header: bytes, sources: list,
+                          overwrite: bool = False, replicas: int = 0,
+                          block_size: int = 0,
+                          storage_tier: str = "") -> FileStatus:
+        """`header` bytes followed by typed tensors (`TypedSource`s, see
+        client/typed_writer.py), each block on the typed store where its
+        content allows.  The layout is checked before the file is created:
+        a refused call leaves nothing behind."""
+        from curvine_amd.client.typed_writer import (TypedFileWriter,
+                                                     validate_layout)
+        validate_layout(header, sources,
+                        block_size or self.conf.client.block_size)
+        st = await self.client.create(path, overwrite, replicas, block_size,
+                                      storage_tier)
+        return await TypedFileWriter(self.client, st, header, sources).run()
+
     async def read_all(self, path: str) -> bytes:
         r = await self.open(path)
         try:

@@ -150,6 +150,19 @@ class Arena:
         unsupported pairs raise ValueError before anything runs."""
         self._n.arena_convert_ptr(self.handle, segments)
 
+    def store_ptr(self, segments: list[tuple]) -> None:
+        """Typed store, the scatter direction of convert_ptr: each segment
+        (src_ptr, dst_off, rows, run, src_pitch, src_dtype, dst_dtype)
+        reads `rows` runs of `run` elements, `src_pitch` bytes apart from
+        the absolute address `src_ptr` (a tensor or a row-strided view of
+        one, aligned to its itemsize), and writes them densely at arena
+        offset `dst_off`, converting src_dtype -> dst_dtype.  Device arena
+        + sources on its GPU = one store_segments_kernel launch for the
+        whole list; host arena + host sources = the same scalar routines in
+        C++.  Bad ranges, alignment, codes and pairs raise ValueError
+        before anything runs.  The sources are free to change on return."""
+        self._n.arena_store_ptr(self.handle, segments)
+
     def lz4_compress(self, off: int, n: int) -> bytes:
         """Compress arena bytes [off, off+n) into a CVLZ container (HIP
         kernel on device arenas: only compressed bytes cross D2H; host

@@ -1,4 +1,4 @@
 from curvine_amd.sdk.fsspec_fs import CurvineFileSystemSpec  # noqa: F401
 from curvine_amd.sdk.torch_io import read_into_tensor, CurvineTensorReader  # noqa: F401
 from curvine_amd.sdk.safetensors_io import (CurvineSafetensors, TensorInfo,  # noqa: F401
-                                            load_file)
+                                            load_file, save_file)

@@ -10,8 +10,12 @@ host hop.  MEM-tier files loaded onto `cpu` run the same segments through
 the same scalar routines in C++; anything else (file tier, cross-side)
 takes the slow, correct pread + host-convert path.
 
-The header parser is written here by hand: the `safetensors` package is
-not a dependency.
+`save_file` is the way back: torch tensors -> a safetensors file in the
+cache, each block written by one `store_segments_kernel` launch where the
+tensors and the arena share a device (see client/typed_writer.py).
+
+The header parser and writer are written here by hand: the `safetensors`
+package is not a dependency.
 """
 from __future__ import annotations
 
@@ -330,3 +334,152 @@ def load_file(sync_fs, path: str, device="cuda:0", dtype=None) -> dict:
     """One-shot: cached safetensors path -> {name: tensor}."""
     with CurvineSafetensors(sync_fs, path) as f:
         return f.load(device=device, dtype=dtype)
+
+
+# ---------------------------------------------------------------- saving
+
+def _rows_of_runs(t):
+    """(rows, run, pitch in elements) when `t`, read in logical order, is
+    rows of contiguous runs — contiguous, or at most one stride break after
+    collapsing contiguous dimensions (`w[:, a:b]`, `w[a:b]`) — else None."""
+    dims = [(n, st) for n, st in zip(t.shape, t.stride()) if n != 1]
+    merged = []
+    for n, st in dims:
+        if merged and merged[-1][1] == st * n:
+            merged[-1] = (merged[-1][0] * n, st)
+        else:
+            merged.append((n, st))
+    if not merged:
+        return 1, 1, 1
+    if len(merged) == 1:
+        n, st = merged[0]
+        if st == 1:
+            return 1, n, n
+        return (n, 1, st) if st > 1 else None
+    if len(merged) == 2:
+        (rows, pitch), (run, st) = merged
+        if st == 1 and pitch >= run:
+            return rows, run, pitch
+    return None
+
+
+def _host_reader(t, rows: int, run: int, pitch: int):
+    """read_host of a TypedSource: dense elements [e0, e1) of `t` as host
+    bytes in the source dtype (only the rows that hold them are copied)."""
+    import torch
+    v = t.as_strided((rows, run), (pitch, 1))
+
+    def read_host(e0: int, e1: int):
+        r0, r1 = e0 // run, (e1 - 1) // run
+        part = v[r0:r1 + 1].reshape(-1)[e0 - r0 * run:e1 - r0 * run]
+        return part.cpu().contiguous().view(torch.uint8).numpy()
+    return read_host
+
+
+def _save_plan(tensors: dict, metadata, dtype):
+    """(header bytes, [TypedSource], tensors kept alive).  Raises before
+    anything touches the cluster."""
+    import torch
+
+    from curvine_amd.client.typed_writer import TypedSource
+    if not isinstance(tensors, dict):
+        raise err.InvalidArgument("safetensors: tensors must be a dict")
+    if metadata is not None and (not isinstance(metadata, dict) or any(
+            not isinstance(k, str) or not isinstance(v, str)
+            for k, v in metadata.items())):
+        raise err.InvalidArgument("safetensors: metadata must map str to str")
+    t2s = {v: k for k, v in _torch_dtypes().items()}
+    entries = []
+    for name, t in tensors.items():
+        if not isinstance(name, str) or name == "__metadata__":
+            raise err.InvalidArgument(f"safetensors: bad tensor name {name!r}")
+        if not isinstance(t, torch.Tensor):
+            raise err.InvalidArgument(
+                f"safetensors: value of {name!r} is not a tensor")
+        if t.layout != torch.strided:
+            raise err.Unsupported(
+                f"safetensors: tensor {name!r}: layout {t.layout}")
+        src = t2s.get(t.dtype)
+        if src is None:
+            raise err.Unsupported(
+                f"safetensors: tensor {name!r}: cannot store {t.dtype}")
+        dst = src
+        if dtype is not None and src in _FLOATING:
+            dst = t2s.get(dtype)
+            if dst is None or not convert_supported(src, dst):
+                raise err.Unsupported(
+                    f"safetensors: tensor {name!r}: cannot save {src} as "
+                    f"{dtype}")
+        if t.device.type == "cpu":
+            device = -1
+        elif t.device.type == "cuda":
+            device = t.device.index
+        else:
+            raise err.InvalidArgument(
+                f"safetensors: tensor {name!r}: unsupported device {t.device}")
+        entries.append((name, t, src, dst, device))
+    entries.sort(key=lambda e: (-DTYPE_ITEMSIZE[e[3]], e[0]))
+
+    hdr, keep, sources, pos = {}, [], [], 0
+    if metadata is not None:
+        hdr["__metadata__"] = dict(metadata)
+    for name, t, src, dst, device in entries:
+        nbytes = t.numel() * DTYPE_ITEMSIZE[dst]
+        hdr[name] = {"dtype": dst, "shape": list(t.shape),
+                     "data_offsets": [pos, pos + nbytes]}
+        if t.numel():
+            lay = _rows_of_runs(t)
+            if lay is None:
+                t = t.contiguous()           # allocates a temporary
+                lay = (1, t.numel(), t.numel())
+            rows, run, pitch = lay
+            keep.append(t)
+            sources.append(TypedSource(
+                pos, t.data_ptr(), rows, run, pitch * DTYPE_ITEMSIZE[src],
+                src, dst, device, _host_reader(t, rows, run, pitch)))
+        pos += nbytes
+    js = json.dumps(hdr, separators=(",", ":")).encode()
+    js += b" " * (-(8 + len(js)) % 64)
+    header = struct.pack("<Q", len(js)) + js
+    for s in sources:
+        s.file_off += len(header)
+    return header, sources, keep
+
+
+def save_file(sync_fs, tensors: dict, path: str, metadata=None, dtype=None,
+              storage_tier: str = "", block_size: int = 0,
+              overwrite: bool = False, replicas: int = 0):
+    """Save {name: tensor} as a safetensors file in the cache; returns its
+    FileStatus.  Blocks that land in the HBM arena of the tensors' own GPU
+    (or in a host arena, for cpu tensors) are written by the typed store:
+    one store_segments_kernel launch per block converts and copies the
+    tensors where they are.  Every other block (file tier, remote worker,
+    replicas > 1, another GPU) is built on the host with the same scalar
+    routines, so the file is bit-identical either way.  cpu and cuda
+    tensors may be mixed.
+
+    File layout: tensors ordered by descending itemsize of the stored
+    dtype, then by name; a contiguous data section; a compact JSON header
+    (`__metadata__` first when given) right-padded with spaces so the data
+    section starts on a multiple of 64.
+
+    `dtype` casts floating tensors where `convert_supported` allows it
+    (integer and bool tensors keep theirs); anything else raises
+    Unsupported.  A tensor is read in place when it is contiguous or rows
+    of contiguous runs (`w[:, a:b]`, `w[a:b]`); any other view is made
+    contiguous first, which allocates a temporary of its size.  Tensors
+    sharing storage are written independently.  `block_size` must be a
+    multiple of 8."""
+    header, sources, keep = _save_plan(tensors, metadata, dtype)
+    devices = sorted({s.device for s in sources if s.device >= 0})
+    if devices:
+        import torch
+        for d in devices:
+            # the store runs on the arena's own stream: what torch's
+            # stream still has in flight for these tensors must be done
+            torch.cuda.current_stream(d).synchronize()
+    st = sync_fs.call(sync_fs.fs.write_typed(
+        path, header, sources, overwrite=overwrite, replicas=replicas,
+        block_size=block_size, storage_tier=storage_tier))
+    del keep
+    return st

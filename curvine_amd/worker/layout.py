@@ -63,6 +63,33 @@ class BlockWriter:
         self.pos = max(self.pos, off + n)
         return n
 
+    def store_typed(self, pieces) -> int:
+        """Typed positional write (checkpoint save): each piece is
+        (block_off, src_ptr, rows, run, src_pitch, src_dt, dst_dt) — rows
+        of `run` source elements `src_pitch` bytes apart at the absolute
+        address `src_ptr`, converted and written densely at `block_off`.
+        One call for the whole list (one kernel launch on HBM).  Like
+        pwrite, `pos` becomes the high watermark; a piece that passes the
+        reservation is refused before anything is written.  Layouts that
+        cannot take a pointer raise Unsupported: the caller then writes
+        bytes.  Returns the bytes written."""
+        from curvine_amd.native import DTYPE_ITEMSIZE, DTYPES
+        isz = {DTYPES[k]: v for k, v in DTYPE_ITEMSIZE.items()}
+        total, top = 0, self.pos
+        for off, _ptr, rows, run, _pitch, _sdt, ddt in pieces:
+            if ddt not in isz:
+                raise err.InvalidArgument(f"store: unknown dtype code {ddt}")
+            n = rows * run * isz[ddt]
+            if off < 0 or off + n > self.meta["reserved"]:
+                raise err.InvalidArgument(
+                    f"typed piece of {n} bytes at {off} passes the block's "
+                    f"reservation {self.meta['reserved']}")
+            total += n
+            top = max(top, off + n)
+        self.layout._store_typed(self.meta, pieces)
+        self.pos = top
+        return total
+
     def write_lz4(self, container) -> int:
         """Append a CVLZ container: decompressed at `pos` (on the GPU for
         HBM blocks); returns the raw size.  Refused before any byte is
@@ -173,6 +200,9 @@ class BlockLayout:
     def _crc(self, meta: dict, off: int, n: int) -> int:
         raise NotImplementedError
 
+    def _store_typed(self, meta: dict, pieces) -> None:
+        raise err.Unsupported(f"typed store to {self.tier} layout")
+
     # LZ4 segments: the defaults stage raw bytes on the host and use the
     # host codec; ArenaLayout overrides both with the arena calls
     def _read_lz4(self, meta: dict, off: int, n: int) -> bytes:
@@ -230,6 +260,15 @@ class ArenaLayout(BlockLayout):
 
     def _write_at_ptr(self, meta, off, ptr, n, device):
         self.arena.write_from_ptr(meta["offset"] + off, ptr, n, device)
+
+    def _store_typed(self, meta, pieces):
+        base = meta["offset"]
+        try:
+            self.arena.store_ptr([(ptr, base + off, rows, run, pitch, sdt, ddt)
+                                  for off, ptr, rows, run, pitch, sdt, ddt
+                                  in pieces])
+        except ValueError as e:
+            raise err.InvalidArgument(str(e))
 
     def _read_at(self, meta, off, n):
         return self.arena.read_bytes(meta["offset"] + off, n)
