@@ -18,12 +18,14 @@
 
 #include <sys/mman.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstring>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
+#include <variant>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -358,6 +360,8 @@ struct Scratch {
     p = (uint8_t*)a->scratch;
     end = p + bytes;
   }
+  // carve device memory the caller owns (calls not tied to an arena)
+  Scratch(void* base, size_t bytes) : p((uint8_t*)base), end(p + bytes) {}
   template <class T> static constexpr size_t align() {
     return sizeof(T) == 1 ? 64 : alignof(T);
   }
@@ -849,22 +853,30 @@ template <class Item> struct DevTiles {
   unsigned grid() const { return std::min<uint32_t>(n_tiles, 8192); }
 };
 
-// carve the three tables (8-byte fields first) and upload them on kstream
+// carve the three tables (8-byte fields first) and upload them on `s`
 template <class Item>
-static DevTiles<Item> upload_tiles(Arena* a, Scratch& sc,
+static DevTiles<Item> upload_tiles(hipStream_t s, Scratch& sc,
                                    const std::vector<Item>& items,
                                    const Tiles& t) {
   Item* d_items = sc.take<Item>(items.size());
   uint64_t* d_off = sc.take<uint64_t>(t.off.size());
   uint32_t* d_item = sc.take<uint32_t>(t.item.size());
   HIP_CHECK(hipMemcpyAsync(d_items, items.data(), items.size() * sizeof(Item),
-                           hipMemcpyHostToDevice, a->kstream));
+                           hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_off, t.off.data(), t.off.size() * sizeof(uint64_t),
-                           hipMemcpyHostToDevice, a->kstream));
+                           hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemcpyAsync(d_item, t.item.data(),
                            t.item.size() * sizeof(uint32_t),
-                           hipMemcpyHostToDevice, a->kstream));
+                           hipMemcpyHostToDevice, s));
   return {d_items, d_item, d_off, (uint32_t)t.item.size()};
+}
+
+// the arena's own scratch and kstream
+template <class Item>
+static DevTiles<Item> upload_tiles(Arena* a, Scratch& sc,
+                                   const std::vector<Item>& items,
+                                   const Tiles& t) {
+  return upload_tiles(a->kstream, sc, items, t);
 }
 
 static Tiles extent_tiles(const std::vector<Extent>& exts, const char* who) {
@@ -976,14 +988,79 @@ static void arena_gather_ptr(
 // ---- typed tensor load (tensor_cast.hip) ----
 //
 // Segments: (src_off, dst_ptr, rows, run, src_pitch, src_dtype, dst_dtype).
+// A 10-tuple appends (scale_ptr, scale_every, scale_e0): F8_E4M3 -> F32/F16/
+// BF16 multiplied by the f32 scale of each element's group.
 // Every argument error is raised here, on the host, before any launch.
 
-static CastSeg cast_validate(uint64_t cap, uint64_t src_off, uint64_t dst_ptr,
-                             uint64_t rows, uint64_t run, uint64_t pitch,
-                             uint64_t sdt, uint64_t ddt) {
+// segment fields as they arrive from Python: 7 without, 10 with a scale
+struct SegArgs {
+  uint64_t a, b, rows, run, pitch, sdt, ddt;
+  uint64_t scale_ptr = 0, scale_every = 0, scale_e0 = 0;
+};
+
+typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                   uint64_t> CastSegTuple;
+typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                   uint64_t, uint64_t, uint64_t, uint64_t> ScaledSegTuple;
+typedef std::variant<CastSegTuple, ScaledSegTuple> AnySegTuple;
+
+static SegArgs seg_args(const AnySegTuple& v) {
+  if (auto* t = std::get_if<CastSegTuple>(&v))
+    return {std::get<0>(*t), std::get<1>(*t), std::get<2>(*t), std::get<3>(*t),
+            std::get<4>(*t), std::get<5>(*t), std::get<6>(*t)};
+  auto& t = std::get<ScaledSegTuple>(v);
+  return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t),
+          std::get<4>(t), std::get<5>(t), std::get<6>(t), std::get<7>(t),
+          std::get<8>(t), std::get<9>(t)};
+}
+
+// The scale fields against the dtype pair (codes already range-checked):
+// a quantising pair needs a scale, F8_E4M3 -> F32/F16/BF16 takes one or is
+// the plain upcast, no other pair takes one.  Returns false when the pair
+// is not a scaled one, for the caller's own pair check.
+static bool scale_validate(const std::string& who, const SegArgs& s,
+                           uint64_t total, bool quant_ok, bool dequant_ok) {
+  bool quant = cast_pair_quantizes((uint32_t)s.sdt, (uint32_t)s.ddt);
+  bool dequant = cast_pair_dequantizes((uint32_t)s.sdt, (uint32_t)s.ddt);
+  if (!s.scale_ptr) {
+    if (quant && quant_ok)
+      throw std::invalid_argument(
+          who + ": unsupported dtype pair without a scale_ptr");
+    return false;
+  }
+  if (!((quant && quant_ok) || (dequant && dequant_ok)))
+    throw std::invalid_argument(who + ": scale_ptr on a dtype pair that takes none");
+  if (s.scale_ptr % 4)
+    throw std::invalid_argument(who + ": scale_ptr misaligned");
+  uint64_t last, bytes, end;
+  if (__builtin_add_overflow(s.scale_e0, total, &last) ||
+      __builtin_mul_overflow(s.scale_every ? last / s.scale_every + 1 : 1,
+                             (uint64_t)4, &bytes) ||
+      __builtin_add_overflow(s.scale_ptr, bytes, &end))
+    throw std::invalid_argument(who + ": scale range overflows");
+  return true;
+}
+
+// [first, last) bytes of the scales a validated scaled segment reads
+static std::pair<uint64_t, uint64_t> scale_span(const CastSeg& g) {
+  uint64_t total = g.rows * g.run;
+  uint64_t g0 = cast_group_of(g.scale_every, g.scale_e0, 0);
+  uint64_t g1 = cast_group_of(g.scale_every, g.scale_e0, total - 1);
+  return {g.scale_ptr + g0 * 4, g.scale_ptr + (g1 + 1) * 4};
+}
+
+static CastSeg cast_validate(uint64_t cap, const SegArgs& in,
+                             bool quant_ok = false) {
+  uint64_t src_off = in.a, dst_ptr = in.b, rows = in.rows, run = in.run,
+           pitch = in.pitch, sdt = in.sdt, ddt = in.ddt;
   if (sdt >= DT_COUNT || ddt >= DT_COUNT)
     throw std::invalid_argument("convert: unknown dtype code");
-  if (sdt != ddt && !cast_pair_converts((uint32_t)sdt, (uint32_t)ddt))
+  uint64_t n_el;
+  if (__builtin_mul_overflow(rows, run, &n_el))
+    throw std::invalid_argument("convert: segment size overflows");
+  bool scaled = scale_validate("convert", in, n_el, quant_ok, true);
+  if (sdt != ddt && !scaled &&
+      !cast_pair_converts((uint32_t)sdt, (uint32_t)ddt))
     throw std::invalid_argument("convert: unsupported dtype pair");
   uint64_t ss = cast_itemsize((uint32_t)sdt), ds = cast_itemsize((uint32_t)ddt);
   uint64_t run_b, span, end, total, dst_b;
@@ -1005,6 +1082,8 @@ static CastSeg cast_validate(uint64_t cap, uint64_t src_off, uint64_t dst_ptr,
   CastSeg g;
   g.src_off = src_off; g.dst_ptr = dst_ptr; g.rows = rows; g.run = run;
   g.src_pitch = pitch; g.src_dt = (uint32_t)sdt; g.dst_dt = (uint32_t)ddt;
+  g.scale_ptr = in.scale_ptr; g.scale_every = in.scale_every;
+  g.scale_e0 = in.scale_e0;
   if (sdt == ddt) {            // raw copy at any itemsize: flatten to bytes
     g.run = run_b;
     g.src_dt = g.dst_dt = DT_U8;
@@ -1012,17 +1091,58 @@ static CastSeg cast_validate(uint64_t cap, uint64_t src_off, uint64_t dst_ptr,
   return g;
 }
 
-typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                   uint64_t> CastSegTuple;
+// a kernel on `device` dereferences [first, last): it has to be memory of
+// that GPU (or pinned host memory), and where the runtime knows the
+// allocation's extent the range has to lie inside it.  `known` holds the
+// allocations already checked in this call: the tensors of a checkpoint
+// mostly share a few allocator blocks, and the runtime queries cost more
+// than the rest of a small call.  Errors read "<who>: <ptr> is not ..." and
+// "<who>: <noun> lives ...".  Caller has set the device.
+static void check_device_range(
+    int device, uint64_t first, uint64_t last, const std::string& who,
+    const char* ptr, const char* noun,
+    std::vector<std::pair<uint64_t, uint64_t>>& known) {
+  for (auto& k : known)
+    if (first >= k.first && last <= k.second) return;
+  hipPointerAttribute_t at;
+  const void* p = (const void*)(uintptr_t)first;
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+    (void)hipGetLastError();
+    throw std::invalid_argument(who + ": " + ptr +
+                                " is not device-visible memory");
+  }
+  if (at.type == hipMemoryTypeDevice && at.device != device)
+    throw std::invalid_argument(who + ": " + noun + " lives on another device");
+  if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost &&
+      at.type != hipMemoryTypeManaged)
+    throw std::invalid_argument(who + ": " + ptr +
+                                " is not device-visible memory");
+  hipDeviceptr_t lo;
+  size_t sz;
+  if (hipMemGetAddressRange(&lo, &sz, (hipDeviceptr_t)p) != hipSuccess) {
+    (void)hipGetLastError();   // extent unknown to the runtime: type check only
+    return;
+  }
+  if (last > (uint64_t)(uintptr_t)lo + sz)
+    throw std::invalid_argument(who + ": " + noun +
+                                " runs past its allocation");
+  known.emplace_back((uint64_t)(uintptr_t)lo, (uint64_t)(uintptr_t)lo + sz);
+}
 
-static void arena_convert_ptr(int h, std::vector<CastSegTuple> segs_in) {
+static void check_scales(int device, const char* who, const CastSeg& g,
+                         std::vector<std::pair<uint64_t, uint64_t>>& known) {
+  if (!g.scale_ptr) return;
+  auto span = scale_span(g);
+  check_device_range(device, span.first, span.second, who, "scale_ptr",
+                     "scales", known);
+}
+
+static void arena_convert_ptr(int h, std::vector<AnySegTuple> segs_in) {
   Arena* a = get_arena(h);
   std::vector<CastSeg> segs;
   segs.reserve(segs_in.size());
   for (auto& t : segs_in) {
-    CastSeg g = cast_validate(a->cap, std::get<0>(t), std::get<1>(t),
-                              std::get<2>(t), std::get<3>(t), std::get<4>(t),
-                              std::get<5>(t), std::get<6>(t));
+    CastSeg g = cast_validate(a->cap, seg_args(t));
     if (g.rows * g.run) segs.push_back(g);
   }
   if (segs.empty()) return;
@@ -1037,6 +1157,8 @@ static void arena_convert_ptr(int h, std::vector<CastSegTuple> segs_in) {
       "convert");
   std::lock_guard<std::mutex> g(a->mu);
   HIP_CHECK(hipSetDevice(a->device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  for (auto& s : segs) check_scales(a->device, "convert", s, known);
   Scratch sc(a, tiles.room<CastSeg>(segs.size()));
   DevTiles<CastSeg> d = upload_tiles(a, sc, segs, tiles);
   launch(convert_segments_kernel, d.grid(), WG, a->kstream,
@@ -1046,18 +1168,35 @@ static void arena_convert_ptr(int h, std::vector<CastSegTuple> segs_in) {
 
 // host conversion of `n` packed elements (the slow path of the typed
 // reader: file-tier extents and elements straddling a block boundary go
-// through the same scalar routines as the kernel)
+// through the same scalar routines as the kernel).  With `scales` (a host
+// buffer of the tensor's f32 group scales) also the scaled pairs in both
+// directions: the byte path of the typed writer quantises here.
 static py::bytes convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
-                              uint64_t n) {
+                              uint64_t n, py::object scales,
+                              uint64_t scale_every, uint64_t scale_e0) {
   py::buffer_info bi = src.request();
+  SegArgs in{0, 0, 1, n, 0, sdt, ddt};
+  py::buffer_info sbi;
+  if (!scales.is_none()) {
+    sbi = py::cast<py::buffer>(scales).request();
+    uint64_t have = (uint64_t)sbi.size * sbi.itemsize / 4, last;
+    if (!sbi.ptr || (uintptr_t)sbi.ptr % 4 || !have)
+      throw std::invalid_argument("convert: scales empty or misaligned");
+    if (n && (__builtin_add_overflow(scale_e0, n - 1, &last) ||
+              (scale_every ? last / scale_every : 0) >= have))
+      throw std::invalid_argument("convert: scales shorter than the groups");
+    in.scale_ptr = (uint64_t)(uintptr_t)sbi.ptr;
+    in.scale_every = scale_every;
+    in.scale_e0 = scale_e0;
+  }
   uint64_t ds = ddt < DT_COUNT ? cast_itemsize((uint32_t)ddt) : 1;
   uint64_t out_b;
   if (__builtin_mul_overflow(n, ds, &out_b) || out_b > (1ull << 40))
     throw std::invalid_argument("convert: segment size overflows");
   // 8-byte words: aligned for every destination itemsize
   std::vector<uint64_t> out(out_b / 8 + 1);
-  CastSeg g = cast_validate((uint64_t)bi.size * bi.itemsize, 0,
-                            (uint64_t)(uintptr_t)out.data(), 1, n, 0, sdt, ddt);
+  in.b = (uint64_t)(uintptr_t)out.data();
+  CastSeg g = cast_validate((uint64_t)bi.size * bi.itemsize, in, true);
   if (g.rows * g.run) convert_segment_host((const uint8_t*)bi.ptr, g);
   return py::bytes((const char*)out.data(), out_b);
 }
@@ -1069,12 +1208,17 @@ static py::bytes convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
 // (a torch tensor or a row-strided view of one), the destination dense at
 // dst_off.  Every argument error is raised here, before any launch.
 
-static CastSeg store_validate(uint64_t cap, uint64_t src_ptr, uint64_t dst_off,
-                              uint64_t rows, uint64_t run, uint64_t pitch,
-                              uint64_t sdt, uint64_t ddt) {
+static CastSeg store_validate(uint64_t cap, const SegArgs& in) {
+  uint64_t src_ptr = in.a, dst_off = in.b, rows = in.rows, run = in.run,
+           pitch = in.pitch, sdt = in.sdt, ddt = in.ddt;
   if (sdt >= DT_COUNT || ddt >= DT_COUNT)
     throw std::invalid_argument("store: unknown dtype code");
-  if (sdt != ddt && !cast_pair_converts((uint32_t)sdt, (uint32_t)ddt))
+  uint64_t n_el;
+  if (__builtin_mul_overflow(rows, run, &n_el))
+    throw std::invalid_argument("store: segment size overflows");
+  bool scaled = scale_validate("store", in, n_el, true, false);
+  if (sdt != ddt && !scaled &&
+      !cast_pair_converts((uint32_t)sdt, (uint32_t)ddt))
     throw std::invalid_argument("store: unsupported dtype pair");
   uint64_t ss = cast_itemsize((uint32_t)sdt), ds = cast_itemsize((uint32_t)ddt);
   uint64_t run_b, span, end, total, dst_b;
@@ -1098,6 +1242,8 @@ static CastSeg store_validate(uint64_t cap, uint64_t src_ptr, uint64_t dst_off,
   CastSeg g;
   g.src_off = src_ptr; g.dst_ptr = dst_off; g.rows = rows; g.run = run;
   g.src_pitch = pitch; g.src_dt = (uint32_t)sdt; g.dst_dt = (uint32_t)ddt;
+  g.scale_ptr = in.scale_ptr; g.scale_every = in.scale_every;
+  g.scale_e0 = in.scale_e0;
   if (sdt == ddt) {            // raw copy at any itemsize: flatten to bytes
     g.run = run_b;
     g.src_dt = g.dst_dt = DT_U8;
@@ -1105,50 +1251,24 @@ static CastSeg store_validate(uint64_t cap, uint64_t src_ptr, uint64_t dst_off,
   return g;
 }
 
-// a device arena's kernel dereferences the source: it has to be memory of
-// the arena's own GPU (or pinned host memory), and where the runtime knows
-// the allocation's extent the segment has to lie inside it.  `known` holds
-// the allocations already checked in this call: the tensors of a checkpoint
-// mostly share a few allocator blocks, and the runtime queries cost more
-// than the rest of a small call.  Caller has set the device.
+// a device arena's kernel dereferences the source (check_device_range)
 static void store_check_source(
     Arena* a, const CastSeg& g,
     std::vector<std::pair<uint64_t, uint64_t>>& known) {
   uint64_t first = g.src_off;
   uint64_t last = first + (g.rows - 1) * g.src_pitch +
                   g.run * cast_itemsize(g.src_dt);   // validated: no overflow
-  for (auto& k : known)
-    if (first >= k.first && last <= k.second) return;
-  hipPointerAttribute_t at;
-  const void* p = (const void*)(uintptr_t)first;
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();
-    throw std::invalid_argument("store: src_ptr is not device-visible memory");
-  }
-  if (at.type == hipMemoryTypeDevice && at.device != a->device)
-    throw std::invalid_argument("store: source lives on another device");
-  if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost &&
-      at.type != hipMemoryTypeManaged)
-    throw std::invalid_argument("store: src_ptr is not device-visible memory");
-  hipDeviceptr_t lo;
-  size_t sz;
-  if (hipMemGetAddressRange(&lo, &sz, (hipDeviceptr_t)p) != hipSuccess) {
-    (void)hipGetLastError();   // extent unknown to the runtime: type check only
-    return;
-  }
-  if (last > (uint64_t)(uintptr_t)lo + sz)
-    throw std::invalid_argument("store: source runs past its allocation");
-  known.emplace_back((uint64_t)(uintptr_t)lo, (uint64_t)(uintptr_t)lo + sz);
+  check_device_range(a->device, first, last, "store", "src_ptr", "source",
+                     known);
+  check_scales(a->device, "store", g, known);
 }
 
-static void arena_store_ptr(int h, std::vector<CastSegTuple> segs_in) {
+static void arena_store_ptr(int h, std::vector<AnySegTuple> segs_in) {
   Arena* a = get_arena(h);
   std::vector<CastSeg> segs;
   segs.reserve(segs_in.size());
   for (auto& t : segs_in) {
-    CastSeg g = store_validate(a->cap, std::get<0>(t), std::get<1>(t),
-                               std::get<2>(t), std::get<3>(t), std::get<4>(t),
-                               std::get<5>(t), std::get<6>(t));
+    CastSeg g = store_validate(a->cap, seg_args(t));
     if (g.rows * g.run) segs.push_back(g);
   }
   if (segs.empty()) return;
@@ -1171,6 +1291,122 @@ static void arena_store_ptr(int h, std::vector<CastSegTuple> segs_in) {
          (uint8_t*)a->base, d.items, d.tile_item, d.tile_off, d.n_tiles);
   // the sources are the caller's to free or overwrite once this returns
   HIP_CHECK(hipStreamSynchronize(a->kstream));
+}
+
+// ---- group scales for the quantising store (tensor_cast.hip) ----
+//
+// Segments: (src_ptr, rows, run, src_pitch, src_dtype, out_ptr, scale_every,
+// scale_e0, n_groups).  out_ptr[0:n_groups] are the f32 scales of the
+// segment's tensor; they are zeroed, receive each group's amax, and become
+// max(amax, 2^-40) / 448.  Segments may share slots (a tensor given in
+// pieces).  Not tied to an arena: a checkpoint's scales are needed before
+// its first block is placed.  device >= 0: absmax_segments_kernel on the
+// caller's thread stream, tables in memory of this call; device == -1: the
+// host loop.  Every argument error is raised before any launch.
+
+typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                   uint64_t, uint64_t, uint64_t> AbsmaxSegTuple;
+
+struct DevFree {
+  void* p = nullptr;
+  ~DevFree() { if (p) (void)hipFree(p); }
+};
+
+static void absmax_scales(int device, std::vector<AbsmaxSegTuple> segs_in) {
+  if (device < -1) throw std::invalid_argument("absmax: bad device");
+  std::vector<AbsmaxSeg> segs;
+  std::vector<ScaleSlots> slots;
+  segs.reserve(segs_in.size());
+  for (auto& t : segs_in) {
+    uint64_t src = std::get<0>(t), rows = std::get<1>(t), run = std::get<2>(t),
+             pitch = std::get<3>(t), sdt = std::get<4>(t),
+             out = std::get<5>(t), every = std::get<6>(t),
+             e0 = std::get<7>(t), n_groups = std::get<8>(t);
+    if (sdt > DT_BF16)
+      throw std::invalid_argument("absmax: source dtype is not F32/F16/BF16");
+    uint64_t ss = cast_itemsize((uint32_t)sdt);
+    uint64_t run_b, total, span, end, last, out_b;
+    if (__builtin_mul_overflow(run, ss, &run_b) ||
+        __builtin_mul_overflow(rows, run, &total) ||
+        __builtin_add_overflow(e0, total, &last) ||
+        __builtin_mul_overflow(n_groups, (uint64_t)4, &out_b) ||
+        __builtin_add_overflow(out, out_b, &end))
+      throw std::invalid_argument("absmax: segment size overflows");
+    if (n_groups == 0 || out == 0 || out % 4)
+      throw std::invalid_argument("absmax: out_ptr null, misaligned or empty");
+    if (total) {
+      if (__builtin_mul_overflow(rows - 1, pitch, &span) ||
+          __builtin_add_overflow(span, run_b, &span) ||
+          __builtin_add_overflow(src, span, &end))
+        throw std::invalid_argument("absmax: source range overflows");
+      if (src == 0 || src % ss)
+        throw std::invalid_argument("absmax: src_ptr null or misaligned");
+      if ((every ? (last - 1) / every : 0) >= n_groups)
+        throw std::invalid_argument("absmax: groups pass n_groups");
+      AbsmaxSeg g;
+      g.src_ptr = src; g.rows = rows; g.run = run; g.src_pitch = pitch;
+      g.out_ptr = out; g.scale_every = every; g.scale_e0 = e0;
+      g.src_dt = (uint32_t)sdt; g.pad = 0;
+      segs.push_back(g);
+    }
+    slots.push_back({out, n_groups});
+  }
+  if (slots.empty()) return;
+  // each slot is zeroed and finished once, however the segments share them
+  std::sort(slots.begin(), slots.end(),
+            [](const ScaleSlots& x, const ScaleSlots& y) { return x.ptr < y.ptr; });
+  std::vector<ScaleSlots> merged;
+  for (auto& r : slots) {
+    if (!merged.empty() && r.ptr <= merged.back().ptr + merged.back().n * 4) {
+      uint64_t end = std::max(merged.back().ptr + merged.back().n * 4,
+                              r.ptr + r.n * 4);
+      merged.back().n = (end - merged.back().ptr) / 4;
+    } else {
+      merged.push_back(r);
+    }
+  }
+  py::gil_scoped_release rel;
+  if (device < 0) {
+    for (auto& r : merged) scale_slots_host(r, false);
+    for (auto& g : segs) absmax_segment_host(g);
+    for (auto& r : merged) scale_slots_host(r, true);
+    return;
+  }
+  Tiles tiles = build_tiles(
+      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
+      [](size_t) { return (uint64_t)CAST_TILE; }, "absmax");
+  HIP_CHECK(hipSetDevice(device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  for (auto& g : segs)
+    check_device_range(device, g.src_ptr,
+                       g.src_ptr + (g.rows - 1) * g.src_pitch +
+                           g.run * cast_itemsize(g.src_dt),
+                       "absmax", "src_ptr", "source", known);
+  for (auto& r : merged)
+    check_device_range(device, r.ptr, r.ptr + r.n * 4, "absmax", "out_ptr",
+                       "scales", known);
+  hipStream_t s = thread_stream(device);
+  size_t room = tiles.room<AbsmaxSeg>(segs.size()) +
+                Scratch::room<ScaleSlots>(merged.size());
+  DevFree mem;
+  HIP_CHECK(hipMalloc(&mem.p, room));
+  Scratch sc(mem.p, room);
+  ScaleSlots* d_slots = sc.take<ScaleSlots>(merged.size());
+  HIP_CHECK(hipMemcpyAsync(d_slots, merged.data(),
+                           merged.size() * sizeof(ScaleSlots),
+                           hipMemcpyHostToDevice, s));
+  unsigned slot_grid = (unsigned)std::min<size_t>(merged.size(), 8192);
+  launch(scale_slots_kernel, slot_grid, WG, s, (const ScaleSlots*)d_slots,
+         (uint32_t)merged.size(), 0);
+  if (!tiles.empty()) {
+    DevTiles<AbsmaxSeg> d = upload_tiles(s, sc, segs, tiles);
+    launch(absmax_segments_kernel, d.grid(), WG, s, d.items, d.tile_item,
+           d.tile_off, d.n_tiles);
+  }
+  launch(scale_slots_kernel, slot_grid, WG, s, (const ScaleSlots*)d_slots,
+         (uint32_t)merged.size(), 1);
+  // the scales are read and the tables freed once this returns
+  HIP_CHECK(hipStreamSynchronize(s));
 }
 
 static uintptr_t arena_base_ptr(int h) {
@@ -1656,6 +1892,13 @@ static void memcpy_h2d(uintptr_t dst, uintptr_t src, uint64_t n) {
   HIP_CHECK(hipMemcpy((void*)dst, (const void*)src, n, hipMemcpyHostToDevice));
 }
 
+// raw device->host copy: the scales of a dequantising load whose extent
+// takes the host convert path
+static void memcpy_d2h(uintptr_t dst, uintptr_t src, uint64_t n) {
+  py::gil_scoped_release rel;
+  HIP_CHECK(hipMemcpy((void*)dst, (const void*)src, n, hipMemcpyDeviceToHost));
+}
+
 static void device_sync(int device) {
   py::gil_scoped_release rel;
   HIP_CHECK(hipSetDevice(device));
@@ -1685,6 +1928,7 @@ PYBIND11_MODULE(_native, m) {
   m.def("device_count", &device_count);
   m.def("device_sync", &device_sync);
   m.def("memcpy_h2d", &memcpy_h2d);
+  m.def("memcpy_d2h", &memcpy_d2h);
   m.def("device_mem_info", &device_mem_info);
   m.def("arena_ipc_handle", &arena_ipc_handle);
   m.def("arena_ipc_open", &arena_ipc_open);
@@ -1703,7 +1947,10 @@ PYBIND11_MODULE(_native, m) {
   m.def("arena_gather_ptr", &arena_gather_ptr);
   m.def("arena_convert_ptr", &arena_convert_ptr);
   m.def("arena_store_ptr", &arena_store_ptr);
-  m.def("convert_host", &convert_host);
+  m.def("convert_host", &convert_host, py::arg("src"), py::arg("src_dtype"),
+        py::arg("dst_dtype"), py::arg("n"), py::arg("scales") = py::none(),
+        py::arg("scale_every") = 0, py::arg("scale_e0") = 0);
+  m.def("absmax_scales", &absmax_scales);
   m.def("arena_base_ptr", &arena_base_ptr);
   m.def("arena_read_batch", &arena_read_batch);
   m.def("reader_register", &reader_register);

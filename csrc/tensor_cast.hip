@@ -17,7 +17,10 @@
 // host loop (`__host__ __device__`), bitwise equal to torch's CPU `.to()`:
 // round-to-nearest-even downcasts, subnormals kept in both directions,
 // overflow to inf, every narrow source widened exactly to f32 first so
-// bf16<->f16 rounds once.
+// bf16<->f16 rounds once.  The scaled fp8 pairs (quantising store F32/F16/
+// BF16 -> F8_E4M3, dequantising load back) add one IEEE f32 divide or
+// multiply by the element's group scale; absmax_segments_kernel computes
+// those scales from the same segments.
 //
 // Access pattern (memory-bound, no LDS): a unit is the element group whose
 // wider side is 16 B, one unit per lane per pass, so both the load and the
@@ -127,6 +130,75 @@ __host__ __device__ inline uint32_t cvt_from_f32(uint32_t f, uint32_t ddt) {
   }
 }
 
+// f32 -> OCP e4m3, saturating: RNE, subnormals kept (smallest 2^-9, exactly
+// 2^-10 ties to 0), |x| >= 448 and inf give +-448, NaN gives 0x7F | sign.
+// Bitwise torch CPU's x.clamp(-448, 448).to(torch.float8_e4m3fn).
+__host__ __device__ inline uint32_t cvt_f32_to_f8e4m3_sat(uint32_t u) {
+  uint32_t sign = (u >> 24) & 0x80u;
+  uint32_t a = u & 0x7FFFFFFFu;
+  if (a > 0x7F800000u) return sign | 0x7Fu;
+  if (a >= 0x43E00000u) return sign | 0x7Eu;            // >= 448
+  if (a < 0x3C800000u) {                                // < 2^-6: subnormal out
+    if (a <= 0x3A800000u) return sign;                  // <= 2^-10 (tie -> even 0)
+    uint32_t e = a >> 23;                               // 117..120
+    uint32_t m = (a & 0x7FFFFFu) | 0x800000u;
+    uint32_t sh = 141u - e;                             // 21..24
+    uint32_t r = m >> sh, rem = m & ((1u << sh) - 1u), half = 1u << (sh - 1u);
+    if (rem > half || (rem == half && (r & 1u))) r++;   // may carry to 0x08
+    return sign | r;
+  }
+  uint32_t r = a - 0x3C000000u;                         // rebias 127 -> 7
+  r += 0x7FFFFu + ((r >> 20) & 1u);                     // RNE; tops out at 0x7E
+  return sign | (r >> 20);
+}
+
+// a quantising pair: F32/F16/BF16 -> F8_E4M3, always with a scale
+__host__ __device__ inline bool cast_pair_quantizes(uint32_t s, uint32_t d) {
+  return s <= DT_BF16 && d == DT_F8_E4M3;
+}
+// a pair that takes a scale on load: F8_E4M3 -> F32/F16/BF16
+__host__ __device__ inline bool cast_pair_dequantizes(uint32_t s, uint32_t d) {
+  return s == DT_F8_E4M3 && d <= DT_BF16;
+}
+
+__host__ __device__ inline float cast_f32_of(uint32_t u) {
+  return __builtin_bit_cast(float, u);
+}
+__host__ __device__ inline uint32_t cast_bits_of(float f) {
+  return __builtin_bit_cast(uint32_t, f);
+}
+
+// scale of a group from the bits of its amax (largest finite |x|):
+// max(amax, 2^-40) / 448, so an all-zero, all-NaN or all-inf group gets
+// 2^-40/448 and no scale is ever denormal
+__host__ __device__ inline uint32_t cast_scale_of_amax(uint32_t amax_bits) {
+  float a = cast_f32_of(amax_bits < 0x2B800000u ? 0x2B800000u : amax_bits);
+  return cast_bits_of(a / 448.0f);
+}
+
+// the scaled element: one correctly rounded f32 divide (quantise) or
+// multiply (dequantise) around the integer conversions.  No reciprocal:
+// it would change bits.
+__host__ __device__ inline uint32_t cvt_scaled(uint32_t bits, uint32_t sdt,
+                                               uint32_t ddt, float scale) {
+  uint32_t f = cvt_to_f32(bits, sdt);
+  if (ddt == DT_F8_E4M3)
+    return cvt_f32_to_f8e4m3_sat(cast_bits_of(cast_f32_of(f) / scale));
+  return cvt_from_f32(cast_bits_of(cast_f32_of(f) * scale), ddt);
+}
+
+// |x| of a source element as an order-preserving key in its own format
+// (widening is monotonic on non-negative finite values, so the max is taken
+// on keys and widened once); 0 for NaN and inf, which the amax skips
+__host__ __device__ inline uint32_t absmax_key(uint32_t bits, uint32_t sdt) {
+  if (sdt == DT_F32) {
+    uint32_t a = bits & 0x7FFFFFFFu;
+    return a > 0x7F7FFFFFu ? 0u : a;
+  }
+  uint32_t a = bits & 0x7FFFu;
+  return a > (sdt == DT_F16 ? 0x7BFFu : 0x7F7Fu) ? 0u : a;
+}
+
 // one element, byte loads, store at the destination itemsize
 __host__ __device__ inline void cast_one(const uint8_t* s, uint8_t* d,
                                          uint32_t sdt, uint32_t ddt) {
@@ -135,6 +207,19 @@ __host__ __device__ inline void cast_one(const uint8_t* s, uint8_t* d,
   for (uint32_t i = 0; i < ss; ++i) bits |= (uint32_t)s[i] << (8u * i);
   uint32_t out = cvt_from_f32(cvt_to_f32(bits, sdt), ddt);
   if (ddt == DT_F32) *reinterpret_cast<uint32_t*>(d) = out;
+  else *reinterpret_cast<uint16_t*>(d) = (uint16_t)out;
+}
+
+// the same for a scaled pair (1-byte store when quantising)
+__host__ __device__ inline void cast_one_scaled(const uint8_t* s, uint8_t* d,
+                                                uint32_t sdt, uint32_t ddt,
+                                                float scale) {
+  uint32_t ss = cast_itemsize(sdt);
+  uint32_t bits = 0;
+  for (uint32_t i = 0; i < ss; ++i) bits |= (uint32_t)s[i] << (8u * i);
+  uint32_t out = cvt_scaled(bits, sdt, ddt, scale);
+  if (ddt == DT_F32) *reinterpret_cast<uint32_t*>(d) = out;
+  else if (ddt == DT_F8_E4M3) *d = (uint8_t)out;
   else *reinterpret_cast<uint16_t*>(d) = (uint16_t)out;
 }
 
@@ -150,7 +235,16 @@ struct CastSeg {
   uint64_t rows, run;   // rows runs of run elements
   uint64_t src_pitch;   // bytes between run starts in the source
   uint32_t src_dt, dst_dt;
+  uint64_t scale_ptr;   // absolute address of the f32 group scales, 0 = unscaled
+  uint64_t scale_every; // dense elements per group, 0 = one group
+  uint64_t scale_e0;    // dense index of element 0 within its tensor: dense
+                        // element e uses scale (scale_e0 + e) / scale_every
 };
+
+__host__ __device__ inline uint64_t cast_group_of(uint64_t every, uint64_t e0,
+                                                  uint64_t e) {
+  return every ? (e0 + e) / every : 0;
+}
 
 // dense destination elements per workgroup tile; same-dtype copies are
 // flattened to bytes by the host and tile at 64 KiB like copy_extents_kernel
@@ -203,8 +297,10 @@ __device__ __forceinline__ void cast_store_words(uint8_t* p,
                                                  const uint32_t (&o)[OW]) {
   if constexpr (OW == 4) {
     *reinterpret_cast<uint4*>(p) = make_uint4(o[0], o[1], o[2], o[3]);
-  } else {
+  } else if constexpr (OW == 2) {
     *reinterpret_cast<uint2*>(p) = make_uint2(o[0], o[1]);
+  } else {
+    *reinterpret_cast<uint32_t*>(p) = o[0];
   }
 }
 
@@ -216,13 +312,17 @@ __device__ __forceinline__ uint32_t cast_extract(const uint32_t* w, int k) {
 }
 
 // one contiguous run of n elements, all WG threads cooperating.
-// SDT == DDT == DT_U8 is the raw byte copy.
-template <uint32_t SDT, uint32_t DDT>
+// SDT == DDT == DT_U8 is the raw byte copy.  SC: a scaled pair, the whole
+// run in one scale group.  A quantising run has a 1-byte destination: K is
+// 4 (F32 source, one dword store per lane) or 8 (16-bit source, uint2
+// store), the head runs up to the first 4- or 8-byte aligned destination
+// byte, and head and tail are byte stores of distinct bytes.
+template <uint32_t SDT, uint32_t DDT, bool SC>
 __device__ __forceinline__ void cast_run(const uint8_t* s, uint8_t* d,
-                                         uint64_t n) {
+                                         uint64_t n, float scale) {
   constexpr bool COPY = (SDT == DDT);
   constexpr int SS = COPY ? 1 : (SDT == DT_F32 ? 4 : (SDT <= DT_BF16 ? 2 : 1));
-  constexpr int DS = COPY ? 1 : (DDT == DT_F32 ? 4 : 2);
+  constexpr int DS = COPY ? 1 : (DDT == DT_F32 ? 4 : (DDT == DT_F8_E4M3 ? 1 : 2));
   constexpr int K = 16 / (SS > DS ? SS : DS);   // elements per unit
   constexpr int W = K * SS / 4;                 // source dwords per unit
   constexpr int OW = K * DS / 4;                // destination dwords per unit
@@ -249,11 +349,17 @@ __device__ __forceinline__ void cast_run(const uint8_t* s, uint8_t* d,
     } else {
 #pragma unroll
       for (int k = 0; k < K; ++k) {
-        uint32_t r = cvt_from_f32(
-            cvt_to_f32(cast_extract<SDT, SS>(w, k), SDT), DDT);
+        uint32_t x = cast_extract<SDT, SS>(w, k), r;
+        if constexpr (SC) r = cvt_scaled(x, SDT, DDT, scale);
+        else r = cvt_from_f32(cvt_to_f32(x, SDT), DDT);
         if constexpr (DS == 4) o[k] = r;
-        else if ((k & 1) == 0) o[k >> 1] = r;
-        else o[k >> 1] |= r << 16;
+        else if constexpr (DS == 2) {
+          if ((k & 1) == 0) o[k >> 1] = r;
+          else o[k >> 1] |= r << 16;
+        } else {
+          if ((k & 3) == 0) o[k >> 2] = r;
+          else o[k >> 2] |= r << ((k & 3) * 8);
+        }
       }
     }
     cast_store_words<OW>(d + (hd + u * K) * DS, o);
@@ -263,23 +369,40 @@ __device__ __forceinline__ void cast_run(const uint8_t* s, uint8_t* d,
   for (uint64_t i = threadIdx.x; i < edge; i += WG) {
     uint64_t e = i < hd ? i : tail0 + (i - hd);
     if constexpr (COPY) d[e] = s[e];
+    else if constexpr (SC) cast_one_scaled(s + e * SS, d + e * DS, SDT, DDT, scale);
     else cast_one(s + e * SS, d + e * DS, SDT, DDT);
   }
 }
 
-template <uint32_t SDT, uint32_t DDT>
+template <uint32_t SDT, uint32_t DDT, bool SC>
 __device__ __forceinline__ void cast_tile(const uint8_t* src, uint8_t* dst,
                                           const CastSeg& g, uint64_t t0,
                                           uint64_t t1) {
   constexpr bool COPY = (SDT == DDT);
   constexpr uint32_t SS = COPY ? 1 : (SDT == DT_F32 ? 4 : (SDT <= DT_BF16 ? 2 : 1));
-  constexpr uint32_t DS = COPY ? 1 : (DDT == DT_F32 ? 4 : 2);
-  if (g.run >= CAST_SHORT_RUN) {
+  constexpr uint32_t DS = COPY ? 1 : (DDT == DT_F32 ? 4 : (DDT == DT_F8_E4M3 ? 1 : 2));
+  const float* scales = reinterpret_cast<const float*>(g.scale_ptr);
+  // groups shorter than a short run (row scales of a narrow tensor) go
+  // element-wise too: one scale fetch per element
+  bool by_run = g.run >= CAST_SHORT_RUN;
+  if constexpr (SC)
+    by_run = by_run && (g.scale_every == 0 || g.scale_every >= CAST_SHORT_RUN);
+  if (by_run) {
     uint64_t e = t0;
     while (e < t1) {                       // workgroup-uniform loop
       uint64_t r = e / g.run, c = e - r * g.run;
       uint64_t len = min(g.run - c, t1 - e);
-      cast_run<SDT, DDT>(src + r * g.src_pitch + c * SS, dst + e * DS, len);
+      float scale = 1.0f;
+      if constexpr (SC) {
+        // a run is cut where its scale group ends (a collapsed layout has
+        // runs longer than a row): one scale fetch per piece
+        uint64_t grp = cast_group_of(g.scale_every, g.scale_e0, e);
+        if (g.scale_every)
+          len = min(len, (grp + 1) * g.scale_every - (g.scale_e0 + e));
+        scale = scales[grp];
+      }
+      cast_run<SDT, DDT, SC>(src + r * g.src_pitch + c * SS, dst + e * DS, len,
+                             scale);
       e += len;
     }
   } else {
@@ -288,6 +411,9 @@ __device__ __forceinline__ void cast_tile(const uint8_t* src, uint8_t* dst,
       uint64_t r = e / g.run, c = e - r * g.run;
       const uint8_t* sp = src + r * g.src_pitch + c * SS;
       if constexpr (COPY) dst[e] = *sp;
+      else if constexpr (SC)
+        cast_one_scaled(sp, dst + e * DS, SDT, DDT,
+                        scales[cast_group_of(g.scale_every, g.scale_e0, e)]);
       else cast_one(sp, dst + e * DS, SDT, DDT);
     }
   }
@@ -301,8 +427,14 @@ __device__ __forceinline__ void cast_segment_tiles(
     const uint8_t* src, uint8_t* dst, const CastSeg& g, uint64_t t0) {
   uint64_t t1 = min(t0 + cast_tile_elems(g.src_dt, g.dst_dt), g.rows * g.run);
 #define CAST_CASE(S, D) \
-  case (S) * 16u + (D): cast_tile<S, D>(src, dst, g, t0, t1); break;
-  switch (g.src_dt * 16u + g.dst_dt) {
+  case (S) * 16u + (D): cast_tile<S, D, false>(src, dst, g, t0, t1); break;
+#define CAST_CASE_SCALED(S, D) \
+  case 256u + (S) * 16u + (D): cast_tile<S, D, true>(src, dst, g, t0, t1); break;
+  switch ((g.scale_ptr ? 256u : 0u) + g.src_dt * 16u + g.dst_dt) {
+    CAST_CASE_SCALED(DT_F32, DT_F8_E4M3) CAST_CASE_SCALED(DT_F16, DT_F8_E4M3)
+    CAST_CASE_SCALED(DT_BF16, DT_F8_E4M3)
+    CAST_CASE_SCALED(DT_F8_E4M3, DT_F32) CAST_CASE_SCALED(DT_F8_E4M3, DT_F16)
+    CAST_CASE_SCALED(DT_F8_E4M3, DT_BF16)
     CAST_CASE(DT_U8, DT_U8)
     CAST_CASE(DT_F32, DT_F16) CAST_CASE(DT_F32, DT_BF16)
     CAST_CASE(DT_F16, DT_F32) CAST_CASE(DT_F16, DT_BF16)
@@ -314,6 +446,7 @@ __device__ __forceinline__ void cast_segment_tiles(
     default: break;   // host rejects every other pair before launch
   }
 #undef CAST_CASE
+#undef CAST_CASE_SCALED
 }
 
 extern "C" __global__ __launch_bounds__(WG) void convert_segments_kernel(
@@ -351,6 +484,14 @@ static void cast_segment_host(const uint8_t* src, uint8_t* dst,
       std::memcpy(d, s, g.run * ss);
       continue;
     }
+    if (g.scale_ptr) {
+      const float* scales = reinterpret_cast<const float*>(g.scale_ptr);
+      for (uint64_t c = 0; c < g.run; ++c)
+        cast_one_scaled(
+            s + c * ss, d + c * ds, g.src_dt, g.dst_dt,
+            scales[cast_group_of(g.scale_every, g.scale_e0, r * g.run + c)]);
+      continue;
+    }
     for (uint64_t c = 0; c < g.run; ++c)
       cast_one(s + c * ss, d + c * ds, g.src_dt, g.dst_dt);
   }
@@ -364,4 +505,176 @@ static void convert_segment_host(const uint8_t* base, const CastSeg& g) {
 static void store_segment_host(uint8_t* base, const CastSeg& g) {
   cast_segment_host(reinterpret_cast<const uint8_t*>(g.src_off),
                     base + g.dst_ptr, g);
+}
+
+// ---------------------------------------------------------------------------
+// absmax: the group scales a quantising store divides by
+// ---------------------------------------------------------------------------
+//
+// The same rows-of-runs segments at an absolute address, reduced instead of
+// stored.  Dense element e of a segment belongs to group
+// (scale_e0 + e) / scale_every of its tensor, whose f32 slot is
+// out_ptr[group].  The slots are zeroed first, hold the bits of the group's
+// amax after absmax_segments_kernel (non-negative f32 patterns order as
+// unsigned integers and max is order-independent: deterministic), and are
+// turned into scales in place by scale_slots_kernel on the same stream.
+
+struct AbsmaxSeg {
+  uint64_t src_ptr;     // absolute address of row 0, aligned to the itemsize
+  uint64_t rows, run;   // rows runs of run elements
+  uint64_t src_pitch;   // bytes between run starts
+  uint64_t out_ptr;     // absolute address of the tensor's f32 group slots
+  uint64_t scale_every; // dense elements per group, 0 = one group
+  uint64_t scale_e0;    // dense index of element 0 within its tensor
+  uint32_t src_dt, pad;
+};
+
+struct ScaleSlots {
+  uint64_t ptr, n;      // n f32 slots at ptr
+};
+
+// per-thread max of the keys of one contiguous run, all WG threads
+// cooperating: 16-byte loads from the first 16-byte aligned source byte,
+// element loads for the head and the tail.  Reads the run's bytes only.
+template <uint32_t SDT>
+__device__ __forceinline__ uint32_t absmax_run(const uint8_t* s, uint64_t n,
+                                               uint32_t m) {
+  constexpr int SS = SDT == DT_F32 ? 4 : 2;
+  constexpr int K = 16 / SS;
+  uint64_t hd = ((0 - (uintptr_t)s) & (uintptr_t)15) / SS;
+  if (hd > n) hd = n;
+  uint64_t nb = (n - hd) / K;
+  const uint8_t* sb = s + hd * SS;
+  for (uint64_t u = threadIdx.x; u < nb; u += WG) {
+    uint32_t w[4];
+    cast_load_words<4>(sb + u * 16, 0, w);
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+      m = max(m, absmax_key(cast_extract<SDT, SS>(w, k), SDT));
+  }
+  uint64_t tail0 = hd + nb * K;
+  uint64_t edge = hd + (n - tail0);
+  for (uint64_t i = threadIdx.x; i < edge; i += WG) {
+    uint64_t e = i < hd ? i : tail0 + (i - hd);
+    uint32_t x;
+    if constexpr (SS == 4) x = *reinterpret_cast<const uint32_t*>(s + e * 4);
+    else x = *reinterpret_cast<const uint16_t*>(s + e * 2);
+    m = max(m, absmax_key(x, SDT));
+  }
+  return m;
+}
+
+// lanes -> wave (cross-lane) -> workgroup (LDS) -> one atomicMax on the slot
+__device__ __forceinline__ void absmax_commit(uint32_t m, uint32_t sdt,
+                                              uint32_t* slot, uint32_t* lds) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o));
+  __syncthreads();                         // the previous commit has read lds
+  if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < WG / 64; ++w) m = max(m, lds[w]);
+    if (m) atomicMax(slot, cvt_to_f32(m, sdt));   // slots start at zero
+  }
+}
+
+template <uint32_t SDT>
+__device__ __forceinline__ void absmax_tile(const AbsmaxSeg& g, uint64_t t0,
+                                            uint64_t t1, uint32_t* lds) {
+  constexpr uint32_t SS = SDT == DT_F32 ? 4 : 2;
+  const uint8_t* src = reinterpret_cast<const uint8_t*>(g.src_ptr);
+  uint32_t* out = reinterpret_cast<uint32_t*>(g.out_ptr);
+  if (g.run >= CAST_SHORT_RUN &&
+      (g.scale_every == 0 || g.scale_every >= CAST_SHORT_RUN)) {
+    uint64_t e = t0, cur = cast_group_of(g.scale_every, g.scale_e0, e);
+    uint32_t m = 0;
+    while (e < t1) {                       // workgroup-uniform loop
+      uint64_t r = e / g.run, c = e - r * g.run;
+      uint64_t len = min(g.run - c, t1 - e);
+      uint64_t grp = cast_group_of(g.scale_every, g.scale_e0, e);
+      if (g.scale_every)
+        len = min(len, (grp + 1) * g.scale_every - (g.scale_e0 + e));
+      if (grp != cur) {
+        absmax_commit(m, SDT, out + cur, lds);
+        m = 0;
+        cur = grp;
+      }
+      m = absmax_run<SDT>(src + r * g.src_pitch + c * SS, len, m);
+      e += len;
+    }
+    absmax_commit(m, SDT, out + cur, lds);
+  } else {
+    // short runs or short groups: element-wise, one atomic per lane per
+    // group it meets (groups only grow along a lane's elements)
+    uint64_t cur = 0;
+    uint32_t m = 0;
+    for (uint64_t e = t0 + threadIdx.x; e < t1; e += WG) {
+      uint64_t r = e / g.run, c = e - r * g.run;
+      const uint8_t* sp = src + r * g.src_pitch + c * SS;
+      uint32_t x;
+      if constexpr (SS == 4) x = *reinterpret_cast<const uint32_t*>(sp);
+      else x = *reinterpret_cast<const uint16_t*>(sp);
+      uint64_t grp = cast_group_of(g.scale_every, g.scale_e0, e);
+      if (grp != cur) {
+        if (m) atomicMax(out + cur, cvt_to_f32(m, SDT));
+        m = 0;
+        cur = grp;
+      }
+      m = max(m, absmax_key(x, SDT));
+    }
+    if (m) atomicMax(out + cur, cvt_to_f32(m, SDT));
+  }
+}
+
+extern "C" __global__ __launch_bounds__(WG) void absmax_segments_kernel(
+    const AbsmaxSeg* __restrict__ segs, const uint32_t* __restrict__ tile_seg,
+    const uint64_t* __restrict__ tile_off, uint32_t n_tiles) {
+  __shared__ uint32_t lds[WG / 64];
+  for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    AbsmaxSeg g = segs[tile_seg[tile]];
+    uint64_t t0 = tile_off[tile];
+    uint64_t t1 = min(t0 + (uint64_t)CAST_TILE, g.rows * g.run);
+    switch (g.src_dt) {
+      case DT_F32: absmax_tile<DT_F32>(g, t0, t1, lds); break;
+      case DT_F16: absmax_tile<DT_F16>(g, t0, t1, lds); break;
+      case DT_BF16: absmax_tile<DT_BF16>(g, t0, t1, lds); break;
+      default: break;   // host rejects every other source before launch
+    }
+  }
+}
+
+// finish == 0: zero the slots; finish != 0: amax bits -> scale bits in place
+extern "C" __global__ __launch_bounds__(WG) void scale_slots_kernel(
+    const ScaleSlots* __restrict__ ranges, uint32_t n_ranges, int finish) {
+  for (uint32_t i = blockIdx.x; i < n_ranges; i += gridDim.x) {
+    uint32_t* p = reinterpret_cast<uint32_t*>(ranges[i].ptr);
+    for (uint64_t k = threadIdx.x; k < ranges[i].n; k += WG)
+      p[k] = finish ? cast_scale_of_amax(p[k]) : 0u;
+  }
+}
+
+// host twins: cpu tensors and host arenas
+static void absmax_segment_host(const AbsmaxSeg& g) {
+  uint32_t ss = cast_itemsize(g.src_dt);
+  uint32_t* out = reinterpret_cast<uint32_t*>(g.out_ptr);
+  for (uint64_t r = 0; r < g.rows; ++r) {
+    const uint8_t* s = reinterpret_cast<const uint8_t*>(g.src_ptr) +
+                       r * g.src_pitch;
+    for (uint64_t c = 0; c < g.run; ++c) {
+      uint32_t bits = 0;
+      for (uint32_t i = 0; i < ss; ++i)
+        bits |= (uint32_t)s[c * ss + i] << (8u * i);
+      uint32_t a = cvt_to_f32(absmax_key(bits, g.src_dt), g.src_dt);
+      uint32_t* slot =
+          out + cast_group_of(g.scale_every, g.scale_e0, r * g.run + c);
+      if (a > *slot) *slot = a;
+    }
+  }
+}
+
+static void scale_slots_host(const ScaleSlots& r, bool finish) {
+  uint32_t* p = reinterpret_cast<uint32_t*>(r.ptr);
+  for (uint64_t k = 0; k < r.n; ++k)
+    p[k] = finish ? cast_scale_of_amax(p[k]) : 0u;
 }

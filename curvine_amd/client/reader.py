@@ -270,7 +270,13 @@ class SyncLocalReader:
         src_dtype, dst_dtype, dst_ptr)] contiguous extents for the
         pread + host-convert path (file tier, cross-side arenas, and the
         single element that can straddle a block boundary when the data
-        section starts at an odd offset)."""
+        section starts at an odd offset).
+
+        A request may append (scale_ptr, scale_every, scale_e0), the
+        dequantising load of Arena.convert_ptr: every piece it is cut into
+        carries the dense index it starts at, so each element keeps its
+        own group's scale; its segments and slow entries are then 10 and 8
+        fields long."""
         import bisect
 
         from curvine_amd.native import DTYPE_ITEMSIZE, DTYPES
@@ -287,12 +293,19 @@ class SyncLocalReader:
                 return None
             return idx
 
-        for off, rows, run, pitch, sdt, ddt, dptr in requests:
+        for off, rows, run, pitch, sdt, ddt, dptr, *scale in requests:
             if rows <= 0 or run <= 0:
                 continue
             ss, ds = DTYPE_ITEMSIZE[sdt], DTYPE_ITEMSIZE[ddt]
             sc, dc = DTYPES[sdt], DTYPES[ddt]
             run_b = run * ss
+
+            def scaled_at(dst):
+                """The scale fields of a piece that lands at dst."""
+                if not scale:
+                    return ()
+                sptr, every, e0 = scale
+                return (sptr, every, e0 + (dst - dptr) // ds)
 
             def emit(idx, pos, n_rows, n_run, dst):
                 """n_rows runs of n_run elements, all inside block idx."""
@@ -304,11 +317,13 @@ class SyncLocalReader:
                 if same_side:
                     _, segs = groups.setdefault(arena.handle, (arena, []))
                     segs.append((r.meta["offset"] + pos - blocks[idx].offset,
-                                 dst, n_rows, n_run, pitch, sc, dc))
+                                 dst, n_rows, n_run, pitch, sc, dc)
+                                + scaled_at(dst))
                 else:
                     for k in range(n_rows):
-                        slow.append((pos + k * pitch, n_run, sdt, ddt,
-                                     dst + k * n_run * ds))
+                        d_k = dst + k * n_run * ds
+                        slow.append((pos + k * pitch, n_run, sdt, ddt, d_k)
+                                    + scaled_at(d_k))
 
             r_i = 0
             while r_i < rows:
@@ -332,12 +347,14 @@ class SyncLocalReader:
                     p = pos + e * ss
                     idx = block_at(p)
                     if idx is None:       # hole: pread synthesizes zeros
-                        slow.append((p, run - e, sdt, ddt, dst + e * ds))
+                        slow.append((p, run - e, sdt, ddt, dst + e * ds)
+                                    + scaled_at(dst + e * ds))
                         break
                     avail = blocks[idx].offset + blocks[idx].block.length - p
                     k = min(run - e, avail // ss)
                     if k == 0:            # element straddles two blocks
-                        slow.append((p, 1, sdt, ddt, dst + e * ds))
+                        slow.append((p, 1, sdt, ddt, dst + e * ds)
+                                    + scaled_at(dst + e * ds))
                         e += 1
                         continue
                     emit(idx, p, 1, k, dst + e * ds)
@@ -354,13 +371,27 @@ class SyncLocalReader:
         from curvine_amd import native
         for arena, segs in groups:
             arena.convert_ptr(segs)
-        for off, n, sdt, ddt, dptr in slow:
+        for off, n, sdt, ddt, dptr, *scale in slow:
+            kw = {}
+            if scale:
+                # the groups this extent touches, fetched to the host
+                sptr, every, e0 = scale
+                g0 = e0 // every if every else 0
+                g1 = (e0 + n - 1) // every if every else 0
+                sbuf = (ctypes.c_float * (g1 - g0 + 1))()
+                if dst_on_device:
+                    native.load().memcpy_d2h(ctypes.addressof(sbuf),
+                                             sptr + 4 * g0, 4 * len(sbuf))
+                else:
+                    ctypes.memmove(sbuf, sptr + 4 * g0, 4 * len(sbuf))
+                kw = {"scales": sbuf, "scale_every": every,
+                      "scale_e0": e0 - g0 * every}
             raw = self.pread(off, n * native.DTYPE_ITEMSIZE[sdt])
             if len(raw) != n * native.DTYPE_ITEMSIZE[sdt]:
                 raise err.OutOfRange(
                     f"typed read at {off}: short read ({len(raw)} bytes)")
             out = native.convert_host(raw, native.DTYPES[sdt],
-                                      native.DTYPES[ddt], n)
+                                      native.DTYPES[ddt], n, **kw)
             if dst_on_device:
                 buf = (ctypes.c_char * len(out)).from_buffer_copy(out)
                 native.load().memcpy_h2d(dptr, ctypes.addressof(buf),

@@ -12,6 +12,12 @@ arena for cpu tensors).  Any other block (file tier, remote worker,
 replicas > 1, sources elsewhere) is materialised on the host, cast with
 `native.convert_host` — the kernel's own scalar routines, so both paths
 give identical bits — and sent through the ordinary block writers.
+
+A source stored as F8_E4M3 carries the f32 scales of its groups
+(`scale_ptr`, `scale_every`): each piece of it tells the store which dense
+element of the tensor it starts at, so a tensor cut by a block boundary
+keeps dividing every row by that row's scale, and the byte path hands the
+same scales to `convert_host`.
 """
 from __future__ import annotations
 
@@ -24,7 +30,8 @@ from curvine_amd.client.block_client import (BlockWriterLocal,
                                              make_block_writer)
 from curvine_amd.client.fs_client import FsClient
 from curvine_amd.model import FileStatus
-from curvine_amd.native import DTYPE_ITEMSIZE, DTYPES, convert_supported
+from curvine_amd.native import (DTYPE_ITEMSIZE, DTYPES, convert_supported,
+                                quantize_supported)
 
 
 @dataclass
@@ -33,7 +40,12 @@ class TypedSource:
     the absolute address `ptr`, stored densely as `dst_dt` from `file_off`.
     `device` is -1 for host memory or the GPU index.  `read_host(e0, e1)`
     returns the source-dtype bytes of dense elements [e0, e1) as a host
-    buffer (the byte path)."""
+    buffer (the byte path).
+
+    Stored as F8_E4M3 the source is quantised: `scale_ptr` is the address
+    (on the source's side) of the f32 scales of its tensor, dense element e
+    using scale e // `scale_every` (0: one scale), and `scales_host()`
+    returns the same scales as a host buffer (the byte path)."""
     file_off: int
     ptr: int
     rows: int
@@ -43,6 +55,13 @@ class TypedSource:
     dst_dt: str
     device: int
     read_host: Callable[[int, int], object]
+    scale_ptr: int = 0
+    scale_every: int = 0
+    scales_host: Callable[[], object] | None = None
+
+    @property
+    def scaled(self) -> bool:
+        return self.scale_ptr != 0
 
     @property
     def numel(self) -> int:
@@ -87,7 +106,15 @@ def validate_layout(header: bytes, sources: list[TypedSource],
         if s.src_dt not in DTYPES or s.dst_dt not in DTYPES:
             raise err.InvalidArgument(
                 f"typed write: unknown dtype {s.src_dt!r}/{s.dst_dt!r}")
-        if not convert_supported(s.src_dt, s.dst_dt):
+        if s.scaled:
+            if s.dst_dt != "F8_E4M3" or not quantize_supported(s.src_dt):
+                raise err.Unsupported(
+                    f"typed write: no scaled store of {s.src_dt} as "
+                    f"{s.dst_dt}")
+            if s.scale_ptr % 4 or s.scale_every < 0 or s.scales_host is None:
+                raise err.InvalidArgument(
+                    "typed write: misaligned or incomplete scale")
+        elif not convert_supported(s.src_dt, s.dst_dt):
             raise err.Unsupported(
                 f"typed write: cannot store {s.src_dt} as {s.dst_dt}")
         ss, ds = DTYPE_ITEMSIZE[s.src_dt], DTYPE_ITEMSIZE[s.dst_dt]
@@ -153,10 +180,15 @@ class TypedFileWriter:
         pieces = []
         for s, off, e0, e1 in parts:
             ds = DTYPE_ITEMSIZE[s.dst_dt]
+            e = e0                    # the piece's first dense element
             for ptr, rows, run in s.pieces(e0, e1):
-                pieces.append((off, ptr, rows, run, s.pitch,
-                               DTYPES[s.src_dt], DTYPES[s.dst_dt]))
+                piece = (off, ptr, rows, run, s.pitch,
+                         DTYPES[s.src_dt], DTYPES[s.dst_dt])
+                if s.scaled:
+                    piece += (s.scale_ptr, s.scale_every, e)
+                pieces.append(piece)
                 off += rows * run * ds
+                e += rows * run
         return pieces
 
     @staticmethod
@@ -166,7 +198,12 @@ class TypedFileWriter:
         buf = bytearray(n)
         for s, off, e0, e1 in parts:
             raw = s.read_host(e0, e1)
-            if s.src_dt != s.dst_dt:
+            if s.scaled:
+                raw = native.convert_host(
+                    raw, DTYPES[s.src_dt], DTYPES[s.dst_dt], e1 - e0,
+                    scales=s.scales_host(), scale_every=s.scale_every,
+                    scale_e0=e0)
+            elif s.src_dt != s.dst_dt:
                 raw = native.convert_host(raw, DTYPES[s.src_dt],
                                           DTYPES[s.dst_dt], e1 - e0)
             raw = memoryview(raw).cast("B")

@@ -147,7 +147,12 @@ class Arena:
         Device arena + device destinations = one convert_segments_kernel
         launch for the whole list; host arena + host destinations = the
         same scalar routines in C++.  Bad ranges, unknown codes and
-        unsupported pairs raise ValueError before anything runs."""
+        unsupported pairs raise ValueError before anything runs.
+
+        A 10-tuple appends (scale_ptr, scale_every, scale_e0) and
+        dequantises F8_E4M3 -> F32/F16/BF16: dense element e is multiplied
+        by the f32 scale at scale_ptr[(scale_e0 + e) // scale_every]
+        (scale_every 0: one scale), memory on the destinations' side."""
         self._n.arena_convert_ptr(self.handle, segments)
 
     def store_ptr(self, segments: list[tuple]) -> None:
@@ -160,7 +165,13 @@ class Arena:
         + sources on its GPU = one store_segments_kernel launch for the
         whole list; host arena + host sources = the same scalar routines in
         C++.  Bad ranges, alignment, codes and pairs raise ValueError
-        before anything runs.  The sources are free to change on return."""
+        before anything runs.  The sources are free to change on return.
+
+        A 10-tuple appends (scale_ptr, scale_every, scale_e0) and quantises
+        F32/F16/BF16 -> F8_E4M3: dense element e is divided by the f32
+        scale at scale_ptr[(scale_e0 + e) // scale_every] (scale_every 0:
+        one scale; see absmax_scales) and cast saturating.  Quantising
+        without a scale_ptr is refused."""
         self._n.arena_store_ptr(self.handle, segments)
 
     def lz4_compress(self, off: int, n: int) -> bytes:
@@ -247,10 +258,45 @@ def convert_supported(src: str, dst: str) -> bool:
     return src == dst or (src in CONVERT_SOURCES and dst in CONVERT_TARGETS)
 
 
-def convert_host(buf, src_dtype: int, dst_dtype: int, n: int) -> bytes:
+# the scaled fp8 pairs: F32/F16/BF16 <-> F8_E4M3 with a group scale
+QUANTIZE_SOURCES = ("F32", "F16", "BF16")
+DEQUANTIZE_TARGETS = ("F32", "F16", "BF16")
+
+
+def quantize_supported(src: str) -> bool:
+    """`src` can be stored as scaled F8_E4M3."""
+    return src in QUANTIZE_SOURCES
+
+
+def dequantize_supported(dst: str) -> bool:
+    """Scaled F8_E4M3 can be loaded as `dst`."""
+    return dst in DEQUANTIZE_TARGETS
+
+
+def convert_host(buf, src_dtype: int, dst_dtype: int, n: int, scales=None,
+                 scale_every: int = 0, scale_e0: int = 0) -> bytes:
     """Convert `n` packed elements on the host with the kernel's own
-    scalar routines (bit-identical to the device path)."""
-    return load().convert_host(buf, src_dtype, dst_dtype, n)
+    scalar routines (bit-identical to the device path).  With `scales` (a
+    host buffer of the tensor's f32 group scales) the scaled pairs too:
+    element i uses scales[(scale_e0 + i) // scale_every], or scales[0]
+    when scale_every is 0."""
+    return load().convert_host(buf, src_dtype, dst_dtype, n, scales,
+                               scale_every, scale_e0)
+
+
+def absmax_scales(device: int, segments: list[tuple]) -> None:
+    """Fill f32 group scales for a quantising store.  Each segment is
+    (src_ptr, rows, run, src_pitch, src_dtype, out_ptr, scale_every,
+    scale_e0, n_groups): `rows` runs of `run` F32/F16/BF16 elements,
+    `src_pitch` bytes apart at `src_ptr`; dense element e belongs to group
+    (scale_e0 + e) // scale_every (0: one group) of its tensor, whose
+    scale is out_ptr[group].  out_ptr[0:n_groups] becomes
+    max(amax, 2**-40) / 448 with amax the largest finite |x| of the group.
+    device >= 0: one absmax_segments_kernel launch for the whole list on
+    that GPU, synchronised on return; device == -1: the same routine in
+    C++ over host memory.  Bad arguments raise ValueError before anything
+    runs."""
+    load().absmax_scales(device, segments)
 
 
 def crc32c(buf, init: int = 0) -> int:

@@ -14,6 +14,16 @@ takes the slow, correct pread + host-convert path.
 cache, each block written by one `store_segments_kernel` launch where the
 tensors and the arena share a device (see client/typed_writer.py).
 
+FP8 checkpoints (a weight plus a `weight_scale`): `save_file(quantize=
+"tensor" | "row")` stores the selected tensors as OCP `F8_E4M3` next to an
+F32 `name + "_scale"`.  The scales come from one `absmax_segments_kernel`
+launch per device for the whole checkpoint and the store divides by them
+as it writes, so the weights are read twice and no full-size temporary
+exists.  `load(dequantize=True)` multiplies such a weight by its scale
+inside the load kernel.  Both directions are bitwise torch CPU's
+`(w.float() / s).clamp(-448, 448).to(float8_e4m3fn)` and
+`(q.float() * s).to(dst)`.
+
 The header parser and writer are written here by hand: the `safetensors`
 package is not a dependency.
 """
@@ -24,8 +34,9 @@ import struct
 from dataclasses import dataclass
 
 from curvine_amd import errors as err
-from curvine_amd.native import (CONVERT_SOURCES, DTYPE_ITEMSIZE,
-                                convert_supported)
+from curvine_amd.native import (CONVERT_SOURCES, DTYPE_ITEMSIZE, DTYPES,
+                                convert_supported, dequantize_supported,
+                                quantize_supported)
 
 MAX_HEADER = 100 << 20
 
@@ -244,6 +255,33 @@ class CurvineSafetensors:
         return (out_shape, outer, part * inner, shape[dim] * inner,
                 rank * part * inner)
 
+    def _scale_info(self, info: TensorInfo):
+        """The F32 `name + "_scale"` entry that makes a stored F8_E4M3
+        tensor a scaled one (one scale, or one per index of dim 0), else
+        None."""
+        if info.dtype != "F8_E4M3":
+            return None
+        s = self._infos.get(info.name + "_scale")
+        if s is None or s.dtype != "F32":
+            return None
+        if s.numel == 1 or (info.shape and s.numel == info.shape[0]):
+            return s
+        return None
+
+    @staticmethod
+    def _scale_fields(info: TensorInfo, sinfo: TensorInfo, shard,
+                      out_shape, scale_ptr: int):
+        """(scale_ptr, scale_every, scale_e0) of a request for `info` or
+        its shard, the tensor's scales being at scale_ptr."""
+        if sinfo.numel == 1:
+            return (scale_ptr, 0, 0)          # ignores the shard
+        every = 1
+        for d in out_shape[1:]:
+            every *= d
+        if shard is not None and shard[0] % len(info.shape) == 0:
+            scale_ptr += 4 * shard[1] * out_shape[0]   # dim-0 shard's rows
+        return (scale_ptr, every, 0)
+
     def _request(self, info: TensorInfo, dst_name: str, shard, dst_ptr: int):
         _, rows, run, pitch_el, first = self._slice(info, shard)
         isz = DTYPE_ITEMSIZE[info.dtype]
@@ -264,18 +302,39 @@ class CurvineSafetensors:
 
     # ---- loading ----
     def load(self, device="cuda:0", dtype=None, names=None,
-             shard_plan=None) -> dict:
+             shard_plan=None, dequantize: bool = False) -> dict:
         """All (or `names`) tensors in one batched pass: every destination
         is allocated, every tensor resolved, then ONE convert call per
-        arena covers the whole file."""
+        arena covers the whole file.
+
+        `dequantize=True`: a stored F8_E4M3 tensor N whose file also holds
+        an F32 `N + "_scale"` with one element or one per index of dim 0
+        comes back multiplied by it, as `dtype` (F32 when None), and the
+        `_scale` entry is left out of the result unless `names` asks for
+        it.  That takes two batched passes: the scales go to F32 tensors
+        on `device` first, then everything else with the weights pointing
+        at them.  An F8_E4M3 tensor without such a scale loads as ever."""
         import torch
         dev = torch.device(device)
         tmap = _torch_dtypes()
         shard_plan = shard_plan or {}
+        wanted = self.keys() if names is None else list(names)
+        scaled = {}
+        if dequantize:
+            for name in wanted:
+                sinfo = self._scale_info(self.info(name))
+                if sinfo is not None:
+                    scaled[name] = sinfo
+            if names is None:
+                hidden = {s.name for s in scaled.values()}
+                wanted = [n for n in wanted if n not in hidden]
         out, requests = {}, []
-        for name in (self.keys() if names is None else names):
+        for name in wanted:
             info = self.info(name)
-            dst_name = self._dst_dtype_name(info, dtype)
+            if name in scaled:
+                dst_name = self._dequant_dtype_name(info, dtype)
+            else:
+                dst_name = self._dst_dtype_name(info, dtype)
             if dst_name not in tmap:
                 raise err.Unsupported(
                     f"safetensors: tensor {name!r}: this torch has no {dst_name}")
@@ -284,19 +343,53 @@ class CurvineSafetensors:
             t = torch.empty(shape, dtype=tmap[dst_name], device=dev)
             out[name] = t
             if t.numel():
-                requests.append(
-                    self._request(info, dst_name, shard, t.data_ptr()))
-        self._execute(requests, dev)
+                requests.append((name, shard, shape, self._request(
+                    info, dst_name, shard, t.data_ptr())))
+        scales = self._load_scales(scaled.values(), dev)
+        self._execute(
+            [req if name not in scaled else req + self._scale_fields(
+                self.info(name), scaled[name], shard, shape,
+                scales[scaled[name].name].data_ptr())
+             for name, shard, shape, req in requests], dev)
         return out
 
-    def get_tensor(self, name: str, device="cuda:0", dtype=None, shard=None):
-        plan = None if shard is None else {name: shard}
-        return self.load(device, dtype, [name], plan)[name]
+    def _dequant_dtype_name(self, info: TensorInfo, dtype) -> str:
+        if dtype is None:
+            return "F32"
+        if self._t2s is None:
+            self._t2s = {v: k for k, v in _torch_dtypes().items()}
+        dst = self._t2s.get(dtype)
+        if dst is None or not dequantize_supported(dst):
+            raise err.Unsupported(
+                f"safetensors: tensor {info.name!r}: cannot dequantize to "
+                f"{dtype}")
+        return dst
 
-    def load_into(self, name: str, tensor, shard=None) -> None:
+    def _load_scales(self, sinfos, dev) -> dict:
+        """{scale name: F32 tensor on dev}, one batched pass."""
+        import torch
+        out, requests = {}, []
+        for s in sinfos:
+            if s.name in out:
+                continue
+            t = torch.empty(s.shape, dtype=torch.float32, device=dev)
+            out[s.name] = t
+            requests.append(self._request(s, "F32", None, t.data_ptr()))
+        if requests:
+            self._execute(requests, dev)
+        return out
+
+    def get_tensor(self, name: str, device="cuda:0", dtype=None, shard=None,
+                   dequantize: bool = False):
+        plan = None if shard is None else {name: shard}
+        return self.load(device, dtype, [name], plan, dequantize)[name]
+
+    def load_into(self, name: str, tensor, shard=None,
+                  dequantize: bool = False) -> None:
         """Fill an existing tensor (a module parameter): destination dtype
-        and device come from `tensor`."""
+        and device come from `tensor`.  `dequantize` as in load()."""
         info = self.info(name)
+        sinfo = self._scale_info(info) if dequantize else None
         shape = self._slice(info, shard)[0]
         if tuple(tensor.shape) != tuple(shape):
             raise err.InvalidArgument(
@@ -311,14 +404,19 @@ class CurvineSafetensors:
                 f"device {tensor.device}")
         t2s = {v: k for k, v in _torch_dtypes().items()}
         dst_name = t2s.get(tensor.dtype)
-        if dst_name is None or not convert_supported(info.dtype, dst_name):
+        if dst_name is None or not (
+                dequantize_supported(dst_name) if sinfo is not None
+                else convert_supported(info.dtype, dst_name)):
             raise err.Unsupported(
                 f"safetensors: tensor {name!r}: cannot load {info.dtype} "
                 f"into {tensor.dtype}")
         if tensor.numel():
-            self._execute(
-                [self._request(info, dst_name, shard, tensor.data_ptr())],
-                tensor.device)
+            req = self._request(info, dst_name, shard, tensor.data_ptr())
+            if sinfo is not None:
+                scales = self._load_scales([sinfo], tensor.device)
+                req += self._scale_fields(info, sinfo, shard, shape,
+                                          scales[sinfo.name].data_ptr())
+            self._execute([req], tensor.device)
 
     def close(self) -> None:
         self.reader.close()
@@ -330,10 +428,11 @@ class CurvineSafetensors:
         self.close()
 
 
-def load_file(sync_fs, path: str, device="cuda:0", dtype=None) -> dict:
+def load_file(sync_fs, path: str, device="cuda:0", dtype=None,
+              dequantize: bool = False) -> dict:
     """One-shot: cached safetensors path -> {name: tensor}."""
     with CurvineSafetensors(sync_fs, path) as f:
-        return f.load(device=device, dtype=dtype)
+        return f.load(device=device, dtype=dtype, dequantize=dequantize)
 
 
 # ---------------------------------------------------------------- saving
@@ -376,10 +475,33 @@ def _host_reader(t, rows: int, run: int, pitch: int):
     return read_host
 
 
-def _save_plan(tensors: dict, metadata, dtype):
+QUANTIZE_MODES = ("tensor", "row")
+
+
+def _quantize_default(name, t) -> bool:
+    return t.is_floating_point() and t.element_size() in (2, 4) and \
+        t.ndim >= 2 and t.numel() > 0
+
+
+def _scales_host(scale):
+    """scales_host of a TypedSource: the f32 scales on the host, fetched
+    once."""
+    cache = []
+
+    def scales_host():
+        if not cache:
+            cache.append(scale.reshape(-1).cpu().numpy())
+        return cache[0]
+    return scales_host
+
+
+def _save_plan(tensors: dict, metadata, dtype, quantize=None,
+               quantize_filter=None):
     """(header bytes, [TypedSource], tensors kept alive).  Raises before
     anything touches the cluster."""
     import torch
+
+    from curvine_amd import native
 
     from curvine_amd.client.typed_writer import TypedSource
     if not isinstance(tensors, dict):
@@ -388,8 +510,15 @@ def _save_plan(tensors: dict, metadata, dtype):
             not isinstance(k, str) or not isinstance(v, str)
             for k, v in metadata.items())):
         raise err.InvalidArgument("safetensors: metadata must map str to str")
+    if quantize is not None and quantize not in QUANTIZE_MODES:
+        raise err.InvalidArgument(
+            f"safetensors: quantize must be one of {QUANTIZE_MODES}, not "
+            f"{quantize!r}")
+    if quantize_filter is None:
+        quantize_filter = _quantize_default
     t2s = {v: k for k, v in _torch_dtypes().items()}
     entries = []
+    n_groups: dict[int, int] = {}        # device -> scale slots needed
     for name, t in tensors.items():
         if not isinstance(name, str) or name == "__metadata__":
             raise err.InvalidArgument(f"safetensors: bad tensor name {name!r}")
@@ -404,7 +533,19 @@ def _save_plan(tensors: dict, metadata, dtype):
             raise err.Unsupported(
                 f"safetensors: tensor {name!r}: cannot store {t.dtype}")
         dst = src
-        if dtype is not None and src in _FLOATING:
+        if quantize is not None and quantize_filter(name, t):
+            if not quantize_supported(src):
+                raise err.Unsupported(
+                    f"safetensors: tensor {name!r}: cannot quantize {src}")
+            if quantize == "row" and t.ndim == 0:
+                raise err.InvalidArgument(
+                    f"safetensors: tensor {name!r}: no dim 0 to scale by")
+            if name + "_scale" in tensors:
+                raise err.InvalidArgument(
+                    f"safetensors: {name + '_scale'!r} is both a given "
+                    f"tensor and the scale of {name!r}")
+            dst = "F8_E4M3"
+        elif dtype is not None and src in _FLOATING:
             dst = t2s.get(dtype)
             if dst is None or not convert_supported(src, dst):
                 raise err.Unsupported(
@@ -418,15 +559,37 @@ def _save_plan(tensors: dict, metadata, dtype):
             raise err.InvalidArgument(
                 f"safetensors: tensor {name!r}: unsupported device {t.device}")
         entries.append((name, t, src, dst, device))
+        if dst != src and dst == "F8_E4M3":
+            n_groups[device] = n_groups.get(device, 0) + (
+                t.shape[0] if quantize == "row" else 1)
+
+    # one F32 buffer per device holds every scale of the checkpoint: each
+    # `name + "_scale"` is a view of it, saved like any given F32 tensor
+    scale_of, used = {}, {}
+    bufs = {d: torch.empty(n, dtype=torch.float32,
+                           device="cpu" if d < 0 else f"cuda:{d}")
+            for d, n in n_groups.items()}
+    for name, t, src, dst, device in list(entries):
+        if dst == src or dst != "F8_E4M3":
+            continue
+        n = t.shape[0] if quantize == "row" else 1
+        o = used.get(device, 0)
+        used[device] = o + n
+        scale = bufs[device][o:o + n].view((n, 1) if quantize == "row"
+                                           else (1,))
+        scale_of[name] = scale
+        entries.append((name + "_scale", scale, "F32", "F32", device))
     entries.sort(key=lambda e: (-DTYPE_ITEMSIZE[e[3]], e[0]))
 
-    hdr, keep, sources, pos = {}, [], [], 0
+    hdr, keep, sources, pos = {}, list(bufs.values()), [], 0
+    absmax: dict[int, list] = {}
     if metadata is not None:
         hdr["__metadata__"] = dict(metadata)
     for name, t, src, dst, device in entries:
         nbytes = t.numel() * DTYPE_ITEMSIZE[dst]
         hdr[name] = {"dtype": dst, "shape": list(t.shape),
                      "data_offsets": [pos, pos + nbytes]}
+        scale = scale_of.get(name) if dst != src else None
         if t.numel():
             lay = _rows_of_runs(t)
             if lay is None:
@@ -434,10 +597,36 @@ def _save_plan(tensors: dict, metadata, dtype):
                 lay = (1, t.numel(), t.numel())
             rows, run, pitch = lay
             keep.append(t)
-            sources.append(TypedSource(
+            source = TypedSource(
                 pos, t.data_ptr(), rows, run, pitch * DTYPE_ITEMSIZE[src],
-                src, dst, device, _host_reader(t, rows, run, pitch)))
+                src, dst, device, _host_reader(t, rows, run, pitch))
+            if scale is not None:
+                # groups follow the tensor's dim 0 whatever the layout
+                # collapsed to
+                every = t.numel() // t.shape[0] if quantize == "row" else 0
+                source.scale_ptr = scale.data_ptr()
+                source.scale_every = every
+                source.scales_host = _scales_host(scale)
+                absmax.setdefault(device, []).append(
+                    (t.data_ptr(), rows, run, source.pitch, DTYPES[src],
+                     scale.data_ptr(), every, 0, scale.numel()))
+            sources.append(source)
         pos += nbytes
+    for device, buf in bufs.items():
+        if not buf.numel():
+            continue
+        if device >= 0:
+            # absmax runs on a stream of its own: what torch's stream
+            # still has in flight for these tensors must be done
+            torch.cuda.current_stream(device).synchronize()
+        segs = absmax.get(device, [])
+        if not segs:                     # only empty weights: floor scales
+            segs = [(0, 0, 0, 0, DTYPES["F32"], buf.data_ptr(), 0, 0,
+                     buf.numel())]
+        try:
+            native.absmax_scales(device, segs)
+        except ValueError as e:
+            raise err.InvalidArgument(str(e))
     js = json.dumps(hdr, separators=(",", ":")).encode()
     js += b" " * (-(8 + len(js)) % 64)
     header = struct.pack("<Q", len(js)) + js
@@ -448,7 +637,8 @@ def _save_plan(tensors: dict, metadata, dtype):
 
 def save_file(sync_fs, tensors: dict, path: str, metadata=None, dtype=None,
               storage_tier: str = "", block_size: int = 0,
-              overwrite: bool = False, replicas: int = 0):
+              overwrite: bool = False, replicas: int = 0, quantize=None,
+              quantize_filter=None):
     """Save {name: tensor} as a safetensors file in the cache; returns its
     FileStatus.  Blocks that land in the HBM arena of the tensors' own GPU
     (or in a host arena, for cpu tensors) are written by the typed store:
@@ -469,8 +659,24 @@ def save_file(sync_fs, tensors: dict, path: str, metadata=None, dtype=None,
     of contiguous runs (`w[:, a:b]`, `w[a:b]`); any other view is made
     contiguous first, which allocates a temporary of its size.  Tensors
     sharing storage are written independently.  `block_size` must be a
-    multiple of 8."""
-    header, sources, keep = _save_plan(tensors, metadata, dtype)
+    multiple of 8.
+
+    `quantize` stores the selected tensors as scaled `F8_E4M3` (OCP E4M3)
+    with their own shape, each next to an F32 `name + "_scale"`:
+    "tensor" gives one scale of shape [1], "row" one per index of dim 0,
+    shape [shape[0], 1].  scale = max(amax, 2**-40) / 448 with amax the
+    largest finite |x| of the group, q = saturate(x / scale), both
+    bitwise torch CPU's.  Selected are the F32/F16/BF16 tensors with
+    ndim >= 2 and numel > 0, or those `quantize_filter(name, tensor)`
+    accepts; everything else is saved as without `quantize`.  Refused
+    before anything touches the cluster: an unknown mode or a
+    `name + "_scale"` that is also a given tensor (InvalidArgument), a
+    selected tensor that is not F32/F16/BF16 (Unsupported).  The scales
+    are computed on the tensors' device, one absmax_segments_kernel launch
+    per device for the whole checkpoint, and views are quantised in
+    place."""
+    header, sources, keep = _save_plan(tensors, metadata, dtype, quantize,
+                                       quantize_filter)
     devices = sorted({s.device for s in sources if s.device >= 0})
     if devices:
         import torch

@@ -72,11 +72,12 @@ class BlockWriter:
         pwrite, `pos` becomes the high watermark; a piece that passes the
         reservation is refused before anything is written.  Layouts that
         cannot take a pointer raise Unsupported: the caller then writes
-        bytes.  Returns the bytes written."""
+        bytes.  A piece may append (scale_ptr, scale_every, scale_e0): the
+        quantising store of Arena.store_ptr.  Returns the bytes written."""
         from curvine_amd.native import DTYPE_ITEMSIZE, DTYPES
         isz = {DTYPES[k]: v for k, v in DTYPE_ITEMSIZE.items()}
         total, top = 0, self.pos
-        for off, _ptr, rows, run, _pitch, _sdt, ddt in pieces:
+        for off, _ptr, rows, run, _pitch, _sdt, ddt, *_scale in pieces:
             if ddt not in isz:
                 raise err.InvalidArgument(f"store: unknown dtype code {ddt}")
             n = rows * run * isz[ddt]
@@ -264,9 +265,8 @@ class ArenaLayout(BlockLayout):
     def _store_typed(self, meta, pieces):
         base = meta["offset"]
         try:
-            self.arena.store_ptr([(ptr, base + off, rows, run, pitch, sdt, ddt)
-                                  for off, ptr, rows, run, pitch, sdt, ddt
-                                  in pieces])
+            self.arena.store_ptr([(p[1], base + p[0]) + tuple(p[2:])
+                                  for p in pieces])
         except ValueError as e:
             raise err.InvalidArgument(str(e))
 
