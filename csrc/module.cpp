@@ -465,29 +465,81 @@ static void bounce_release(BouncePair* b) {
 // per-caller-thread stream: zero contention for concurrent small copies
 // (the 4K-IOPS path).  hipMemcpy on the null stream and ROCm's internal
 // pageable-staging lock both serialize; a thread_local stream does not.
-// Streams are destroyed when their thread exits (no leak under thread
-// churn) — except during process teardown, when the HIP runtime may
-// already be gone.
+// A thread that exits parks its streams on a per-device free list (bounded:
+// no leak under thread churn) and the next new thread takes one from there,
+// so short-lived reader threads pay no stream create/destroy — except
+// during process teardown, when the HIP runtime may already be gone.
 static std::atomic<bool> g_process_exiting{false};
 static struct ExitFlagSetter {
   ~ExitFlagSetter() { g_process_exiting.store(true); }
 } g_exit_flag_setter;
 
+// counters behind hip_pool_stats()
+static std::atomic<uint64_t> g_st_pinned_created{0}, g_st_pinned_reused{0},
+    g_st_streams_created{0}, g_st_streams_reused{0}, g_st_reader_pread{0};
+
+static constexpr int kMaxDevices = 64;
+static constexpr size_t kStreamPoolPerDev = 64;
+
+struct StreamPool {
+  std::mutex mu;
+  std::vector<hipStream_t> free_by_dev[kMaxDevices];
+};
+
+// leaked on purpose: thread_local destructors of late-exiting threads run
+// after static destructors would have torn a plain static down
+static StreamPool& stream_pool() {
+  static StreamPool* p = new StreamPool();
+  return *p;
+}
+
 struct TlsStreams {
-  hipStream_t s[64] = {};
+  hipStream_t s[kMaxDevices] = {};
   ~TlsStreams() {
     if (g_process_exiting.load()) return;
-    for (auto x : s)
+    for (int d = 0; d < kMaxDevices; ++d) {
+      hipStream_t x = s[d];
+      if (!x) continue;
+      // a parked stream must be idle: its next owner syncs on it
+      if (hipStreamQuery(x) != hipSuccess) {
+        (void)hipGetLastError();
+        (void)hipStreamSynchronize(x);
+      }
+      StreamPool& p = stream_pool();
+      {
+        std::lock_guard<std::mutex> g(p.mu);
+        if (p.free_by_dev[d].size() < kStreamPoolPerDev) {
+          p.free_by_dev[d].push_back(x);
+          x = nullptr;
+        }
+      }
       if (x) (void)hipStreamDestroy(x);
+    }
   }
 };
 
 static hipStream_t thread_stream(int device) {
   thread_local TlsStreams tls;
-  if (device < 0 || device >= 64) throw std::runtime_error("bad device");
+  if (device < 0 || device >= kMaxDevices)
+    throw std::runtime_error("bad device");
   if (!tls.s[device]) {
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&tls.s[device], hipStreamNonBlocking));
+    StreamPool& p = stream_pool();
+    {
+      std::lock_guard<std::mutex> g(p.mu);
+      auto& v = p.free_by_dev[device];
+      if (!v.empty()) {
+        tls.s[device] = v.back();
+        v.pop_back();
+      }
+    }
+    if (tls.s[device]) {
+      g_st_streams_reused.fetch_add(1, std::memory_order_relaxed);
+    } else {
+      HIP_CHECK(hipSetDevice(device));
+      HIP_CHECK(hipStreamCreateWithFlags(&tls.s[device],
+                                         hipStreamNonBlocking));
+      g_st_streams_created.fetch_add(1, std::memory_order_relaxed);
+    }
   }
   return tls.s[device];
 }
@@ -1448,23 +1500,25 @@ static void arena_read_batch(int h, const std::vector<uint64_t>& offs,
 struct RdExt { uint64_t file_off, len; int arena; uint64_t arena_off; };
 struct RdReader { uint64_t length; std::vector<RdExt> exts; };
 static std::mutex g_rd_mu;
-static std::unordered_map<int64_t, RdReader> g_rd;
+// shared_ptr: a read keeps its reader alive past the lock, whatever the map
+// does meanwhile (rehash, a racing unregister)
+static std::unordered_map<int64_t, std::shared_ptr<const RdReader>> g_rd;
 static int64_t g_rd_next = 1;
 
 static int64_t reader_register(
     std::vector<std::tuple<uint64_t, uint64_t, int, uint64_t>> exts,
     uint64_t length) {
-  RdReader r;
-  r.length = length;
-  r.exts.reserve(exts.size());
+  auto r = std::make_shared<RdReader>();
+  r->length = length;
+  r->exts.reserve(exts.size());
   uint64_t prev = 0;
   for (auto& e : exts) {
     if (std::get<0>(e) < prev)
       throw std::runtime_error("reader_register: extents must be sorted");
     prev = std::get<0>(e);
     get_arena(std::get<2>(e));   // validate handle
-    r.exts.push_back({std::get<0>(e), std::get<1>(e), std::get<2>(e),
-                      std::get<3>(e)});
+    r->exts.push_back({std::get<0>(e), std::get<1>(e), std::get<2>(e),
+                       std::get<3>(e)});
   }
   std::lock_guard<std::mutex> g(g_rd_mu);
   int64_t rid = g_rd_next++;
@@ -1477,6 +1531,61 @@ static void reader_unregister(int64_t rid) {
   g_rd.erase(rid);
 }
 
+static std::shared_ptr<const RdReader> rd_get(int64_t rid) {
+  std::lock_guard<std::mutex> g(g_rd_mu);
+  auto it = g_rd.find(rid);
+  if (it == g_rd.end()) throw std::runtime_error("bad reader id");
+  return it->second;
+}
+
+// the extent search shared by reader_pread_batch and reader_pread: the
+// extent that holds file offset `off`, or nullptr when `off` lies in a hole
+// or past the last extent
+static const RdExt* rd_ext_at(const std::vector<RdExt>& exts, uint64_t off) {
+  // binary search: last extent with file_off <= off
+  size_t lo = 0, hi = exts.size();
+  while (lo < hi) {
+    size_t mid = (lo + hi) / 2;
+    if (exts[mid].file_off <= off) lo = mid + 1; else hi = mid;
+  }
+  if (lo == 0) return nullptr;
+  const RdExt* e = &exts[lo - 1];
+  return off - e->file_off < e->len ? e : nullptr;
+}
+
+// devices whose thread streams carry copies of the current call: one
+// hipStreamSynchronize each at the end
+struct RdDevSet {
+  int dev[8];
+  int n = 0;
+  void add(int d) {
+    for (int i = 0; i < n; i++) if (dev[i] == d) return;
+    if (n < 8) { dev[n++] = d; return; }
+    // a ninth device: drain it now, the set stays exact
+    HIP_CHECK(hipStreamSynchronize(thread_stream(d)));
+  }
+  void sync() {
+    for (int i = 0; i < n; i++) {
+      HIP_CHECK(hipSetDevice(dev[i]));
+      HIP_CHECK(hipStreamSynchronize(thread_stream(dev[i])));
+    }
+  }
+};
+
+// one arena -> host piece: memcpy, or an async D2H on the thread stream
+static void rd_issue(Arena* a, uint64_t aoff, uint8_t* dst, uint64_t n,
+                     RdDevSet& devs) {
+  const uint8_t* src = (const uint8_t*)a->base + aoff;
+  if (!a->is_dev()) {
+    std::memcpy(dst, src, n);
+    return;
+  }
+  HIP_CHECK(hipSetDevice(a->device));
+  HIP_CHECK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost,
+                           thread_stream(a->device)));
+  devs.add(a->device);
+}
+
 // fixed-size batched preads: for each file offset, land n bytes at
 // dst_ptr + i*stride.  Returns the indices it could NOT serve (reads
 // spanning extent boundaries or past EOF) so the caller falls back for
@@ -1485,59 +1594,68 @@ static py::list reader_pread_batch(int64_t rid,
                                    const std::vector<uint64_t>& offs,
                                    uint64_t n, uintptr_t dst_ptr,
                                    uint64_t stride) {
-  RdReader* r;
-  {
-    std::lock_guard<std::mutex> g(g_rd_mu);
-    auto it = g_rd.find(rid);
-    if (it == g_rd.end()) throw std::runtime_error("bad reader id");
-    r = &it->second;
-  }
+  std::shared_ptr<const RdReader> r = rd_get(rid);
   std::vector<uint32_t> skipped;
   {
     py::gil_scoped_release rel;
-    int used_dev[8];
-    int n_dev = 0;
-    const auto& exts = r->exts;
+    RdDevSet devs;
     for (size_t i = 0; i < offs.size(); ++i) {
       uint64_t off = offs[i];
       const RdExt* e = nullptr;
-      if (off + n <= r->length && !exts.empty()) {
-        // binary search: last extent with file_off <= off
-        size_t lo = 0, hi = exts.size();
-        while (lo < hi) {
-          size_t mid = (lo + hi) / 2;
-          if (exts[mid].file_off <= off) lo = mid + 1; else hi = mid;
-        }
-        if (lo > 0 && off - exts[lo - 1].file_off + n <= exts[lo - 1].len)
-          e = &exts[lo - 1];
+      if (off + n <= r->length) {
+        e = rd_ext_at(r->exts, off);
+        if (e && off - e->file_off + n > e->len) e = nullptr;
       }
       if (e == nullptr) {
         skipped.push_back((uint32_t)i);
         continue;
       }
-      uint64_t boff = off - e->file_off;
-      Arena* a = get_arena(e->arena);
-      uint8_t* dst = (uint8_t*)dst_ptr + i * stride;
-      const uint8_t* src = (uint8_t*)a->base + e->arena_off + boff;
-      if (!a->is_dev()) {
-        std::memcpy(dst, src, n);
-      } else {
-        HIP_CHECK(hipSetDevice(a->device));
-        HIP_CHECK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost,
-                                 thread_stream(a->device)));
-        bool seen = false;
-        for (int d = 0; d < n_dev; d++) seen |= (used_dev[d] == a->device);
-        if (!seen && n_dev < 8) used_dev[n_dev++] = a->device;
-      }
+      rd_issue(get_arena(e->arena), e->arena_off + (off - e->file_off),
+               (uint8_t*)dst_ptr + i * stride, n, devs);
     }
-    for (int d = 0; d < n_dev; d++) {
-      HIP_CHECK(hipSetDevice(used_dev[d]));
-      HIP_CHECK(hipStreamSynchronize(thread_stream(used_dev[d])));
-    }
+    devs.sync();
   }
   py::list out;
   for (uint32_t i : skipped) out.append(i);
   return out;
+}
+
+// one ranged pread, GIL-free: [off, off+n) clamped to the reader's length
+// lands at dst_ptr, one copy per extent the range covers (a read across a
+// block boundary stays native) and one synchronise per device used.
+// Returns the bytes served, or -1 with nothing issued when any part of the
+// range is not covered by a registered extent (hole, sparse tail): the
+// caller's Python loop serves those.
+static int64_t reader_pread(int64_t rid, uint64_t off, uint64_t n,
+                            uintptr_t dst_ptr) {
+  std::shared_ptr<const RdReader> r = rd_get(rid);
+  g_st_reader_pread.fetch_add(1, std::memory_order_relaxed);
+  if (off >= r->length) return 0;
+  n = std::min<uint64_t>(n, r->length - off);
+  if (n == 0) return 0;
+  py::gil_scoped_release rel;
+  struct Piece { Arena* a; uint64_t aoff, n; };
+  std::vector<Piece> pieces;
+  pieces.reserve(2);
+  // resolve and validate the whole range first: -1 must issue nothing
+  for (uint64_t got = 0; got < n;) {
+    const RdExt* e = rd_ext_at(r->exts, off + got);
+    if (e == nullptr) return -1;
+    uint64_t boff = off + got - e->file_off;
+    uint64_t len = std::min<uint64_t>(n - got, e->len - boff);
+    Arena* a = get_arena(e->arena);
+    check_range(a, e->arena_off + boff, len);
+    pieces.push_back({a, e->arena_off + boff, len});
+    got += len;
+  }
+  RdDevSet devs;
+  uint8_t* dst = (uint8_t*)dst_ptr;
+  for (const Piece& p : pieces) {
+    rd_issue(p.a, p.aoff, dst, p.n, devs);
+    dst += p.n;
+  }
+  devs.sync();
+  return (int64_t)n;
 }
 
 // ---------------------------------------------------------------------------
@@ -1836,29 +1954,100 @@ struct PinnedBuf { void* ptr = nullptr; size_t n = 0; bool pinned = false; };
 static std::vector<PinnedBuf> g_pins;
 static std::mutex g_pins_mu;
 
-static int pinned_alloc(size_t n) {
-  PinnedBuf b;
-  b.n = n;
-  if (device_count() > 0) {
-    HIP_CHECK(hipHostMalloc(&b.ptr, n, hipHostMallocDefault));
-    b.pinned = true;
-  } else {
-    b.ptr = std::malloc(n);
-    if (!b.ptr) throw std::bad_alloc();
-  }
-  std::lock_guard<std::mutex> g(g_pins_mu);
+// hipHostMalloc costs ~1 ms and hipHostFree waits on the device, so freed
+// buffers park on a free list and the next pinned_alloc of exactly that
+// byte size takes the newest one back (malloc'd buffers without a GPU go
+// the same way).  Bounded by count and by total bytes: what no longer fits
+// is freed as before, oldest parked buffer first, so sizes nobody asks for
+// any more cannot hold the pool.  A buffer above the per-buffer cap is never
+// parked.  Contract: a caller frees a buffer only after its reads into it
+// have returned — parking does no device sync, and the contents of a fresh
+// buffer are unspecified, as they always were.  Parked buffers live until
+// they are evicted or the process exits.
+static constexpr size_t kPinPoolMaxBuf = 64u << 20;
+static constexpr size_t kPinPoolMaxCount = 64;
+static constexpr size_t kPinPoolMaxBytes = 512u << 20;
+static std::vector<PinnedBuf> g_pin_pool;   // oldest first; g_pins_mu
+static size_t g_pin_pool_bytes = 0;         // g_pins_mu
+
+static int pinned_publish(const PinnedBuf& b) {   // g_pins_mu held
   for (size_t i = 0; i < g_pins.size(); ++i)
     if (!g_pins[i].ptr) { g_pins[i] = b; return (int)i; }
   g_pins.push_back(b);
   return (int)g_pins.size() - 1;
 }
 
-static void pinned_free(int id) {
+static void pinned_release(const PinnedBuf& b) {
+  if (b.pinned) hipHostFree(b.ptr);
+  else std::free(b.ptr);
+}
+
+static int pinned_alloc(size_t n) {
+  {
+    std::lock_guard<std::mutex> g(g_pins_mu);
+    for (size_t i = g_pin_pool.size(); i-- > 0;) {
+      if (g_pin_pool[i].n != n) continue;
+      PinnedBuf b = g_pin_pool[i];
+      g_pin_pool.erase(g_pin_pool.begin() + i);
+      g_pin_pool_bytes -= b.n;
+      g_st_pinned_reused.fetch_add(1, std::memory_order_relaxed);
+      return pinned_publish(b);
+    }
+  }
+  PinnedBuf b;
+  b.n = n;
+  if (device_count() > 0) {
+    HIP_CHECK(hipHostMalloc(&b.ptr, n, hipHostMallocDefault));
+    b.pinned = true;
+  } else {
+    b.ptr = std::malloc(n ? n : 1);
+    if (!b.ptr) throw std::bad_alloc();
+  }
+  g_st_pinned_created.fetch_add(1, std::memory_order_relaxed);
   std::lock_guard<std::mutex> g(g_pins_mu);
-  if (id < 0 || id >= (int)g_pins.size() || !g_pins[id].ptr) return;
-  if (g_pins[id].pinned) hipHostFree(g_pins[id].ptr);
-  else std::free(g_pins[id].ptr);
-  g_pins[id] = PinnedBuf{};
+  return pinned_publish(b);
+}
+
+static void pinned_free(int id) {
+  std::vector<PinnedBuf> drop;   // freed outside the lock: hipHostFree
+                                 // waits on the device
+  {
+    std::lock_guard<std::mutex> g(g_pins_mu);
+    if (id < 0 || id >= (int)g_pins.size() || !g_pins[id].ptr) return;
+    PinnedBuf b = g_pins[id];
+    g_pins[id] = PinnedBuf{};
+    if (b.n > kPinPoolMaxBuf) {
+      drop.push_back(b);
+    } else {
+      g_pin_pool.push_back(b);
+      g_pin_pool_bytes += b.n;
+      while (g_pin_pool.size() > kPinPoolMaxCount ||
+             g_pin_pool_bytes > kPinPoolMaxBytes) {
+        drop.push_back(g_pin_pool.front());
+        g_pin_pool_bytes -= g_pin_pool.front().n;
+        g_pin_pool.erase(g_pin_pool.begin());
+      }
+    }
+  }
+  for (const PinnedBuf& b : drop) pinned_release(b);
+}
+
+static py::dict hip_pool_stats() {
+  py::dict d;
+  d["pinned_created"] = g_st_pinned_created.load();
+  d["pinned_reused"] = g_st_pinned_reused.load();
+  {
+    std::lock_guard<std::mutex> g(g_pins_mu);
+    d["pinned_parked_bytes"] = g_pin_pool_bytes;
+    d["pinned_parked_count"] = g_pin_pool.size();
+  }
+  d["pinned_pool_max_count"] = kPinPoolMaxCount;
+  d["pinned_pool_max_bytes"] = kPinPoolMaxBytes;
+  d["pinned_pool_max_buffer"] = kPinPoolMaxBuf;
+  d["streams_created"] = g_st_streams_created.load();
+  d["streams_reused"] = g_st_streams_reused.load();
+  d["reader_pread_calls"] = g_st_reader_pread.load();
+  return d;
 }
 
 static py::memoryview pinned_view(int id) {
@@ -1956,6 +2145,8 @@ PYBIND11_MODULE(_native, m) {
   m.def("reader_register", &reader_register);
   m.def("reader_unregister", &reader_unregister);
   m.def("reader_pread_batch", &reader_pread_batch);
+  m.def("reader_pread", &reader_pread);
+  m.def("hip_pool_stats", &hip_pool_stats);
   m.def("arena_info", &arena_info);
   m.def("arena_dlpack", &arena_dlpack);
   m.def("arena_host_view", &arena_host_view);

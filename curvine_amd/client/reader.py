@@ -108,7 +108,8 @@ class SyncLocalReader:
             return
         try:
             from curvine_amd import native
-            self._native_rid = native.load().reader_register(
+            self._native = native.load()
+            self._native_rid = self._native.reader_register(
                 exts, self.length)
         except Exception:  # noqa: BLE001 — extension absent on this host
             self._native_rid = None
@@ -135,7 +136,14 @@ class SyncLocalReader:
         return got
 
     def pread_into_ptr(self, off: int, ptr: int, n: int) -> int:
-        """Pinned/device-pointer destination (direct DMA)."""
+        """Pinned/device-pointer destination (direct DMA).  A registered
+        reader serves the whole range in one GIL-free native call
+        (reader_pread: block-spanning reads included); holes, sparse tails
+        and unregistered readers take the Python loop below."""
+        if self._native_rid is not None and off >= 0 and n > 0:
+            got = self._native.reader_pread(self._native_rid, off, n, ptr)
+            if got >= 0:
+                return got
         import bisect
         import ctypes
         n = max(0, min(n, self.length - off))
@@ -169,6 +177,12 @@ class SyncLocalReader:
         issue async on one thread-local stream with ONE sync; anything
         else (file tier, block-spanning) falls back per-read.  Returns the
         number of reads served."""
+        if self._native_rid is not None and len(file_offs) == 1:
+            # a batch of one is a ranged read (the sequential path at
+            # depth 1): no offset list to convert, block-spanning included
+            if self._native.reader_pread(self._native_rid, file_offs[0], n,
+                                         dst_ptr) == n:
+                return 1
         import bisect
         import ctypes
         from curvine_amd import native

@@ -216,10 +216,23 @@ class Arena:
             pass
 
 
+def hip_pool_stats() -> dict:
+    """Counters of the native pinned-buffer and stream pools and of the
+    native ranged pread: pinned_created / pinned_reused (allocations made
+    vs. served from the free list), pinned_parked_bytes / _count (idle in
+    the pool now), pinned_pool_max_count / _max_bytes / _max_buffer (the
+    pool's bounds), streams_created / streams_reused, reader_pread_calls."""
+    return dict(load().hip_pool_stats())
+
+
 class PinnedBuffer:
     """hipHostMalloc'd buffer (plain malloc without a GPU): DMA-fast host
     memory exposed as a writable memoryview.  Used for FUSE request/reply
-    buffers so device reads land directly in the bytes handed to writev."""
+    buffers so device reads land directly in the bytes handed to writev.
+
+    close() parks the memory in a native pool for the next PinnedBuffer of
+    the same size, without a device sync: close only after every read into
+    the buffer has returned.  Contents of a new buffer are unspecified."""
 
     def __init__(self, nbytes: int):
         self._n = load()
