@@ -151,6 +151,7 @@ static uint32_t crc32c_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
 
 #include "lz4.hip"
 #include "tensor_cast.hip"
+#include "mx_cast.hip"
 
 // ---------------------------------------------------------------------------
 // GPU availability
@@ -1461,6 +1462,260 @@ static void absmax_scales(int device, std::vector<AbsmaxSegTuple> segs_in) {
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// ---- MX tensors: E8M0 block scales, E4M3 / E2M1 elements (mx_cast.hip) ----
+//
+// Entry points of their own beside absmax_scales, store_ptr, convert_ptr
+// and convert_host; the dtype codes of those stay as they are.  A segment
+// names its high-precision side (F32/F16/BF16) and its stored side
+// (F8_E4M3, or F4 = code 17) and carries (scale_ptr, scale_e0, scale_pitch,
+// 32): the element in row r, column c uses the E8M0 byte at
+// scale_ptr[(scale_e0 + r * scale_pitch + c) / 32].  Every argument error
+// is raised on the host before any launch.
+
+enum MxKind { MX_SCALES, MX_STORE, MX_LOAD };
+
+struct MxArgs {
+  uint64_t a, b, rows, run, pitch, hp_dt, stored_dt, scale_ptr, scale_e0,
+      scale_pitch, block;
+};
+
+typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                   uint64_t, uint64_t, uint64_t, uint64_t, uint64_t> MxSegTuple;
+
+// kind MX_SCALES / MX_STORE: a = absolute source; MX_STORE: b = arena
+// offset; MX_LOAD: a = arena offset, b = absolute destination
+static MxSeg mx_validate(const std::string& who, MxKind kind, uint64_t cap,
+                         const MxArgs& in) {
+  if (in.block != MX_BLOCK)
+    throw std::invalid_argument(who + ": block size is not 32");
+  if (in.hp_dt > DT_BF16)
+    throw std::invalid_argument(who + ": not F32/F16/BF16 on the wide side");
+  if (in.stored_dt != DT_F8_E4M3 && in.stored_dt != DT_F4)
+    throw std::invalid_argument(who + ": stored dtype is not F8_E4M3 or F4");
+  uint32_t fmt = in.stored_dt == DT_F4 ? MX_E2M1 : MX_E4M3;
+  uint64_t hs = cast_itemsize((uint32_t)in.hp_dt), bits = mx_bits(fmt);
+  uint64_t ss = kind == MX_LOAD ? 1 : hs;            // source alignment
+  uint64_t total, run_b, q_b, hp_b, span, end, last;
+  if (__builtin_mul_overflow(in.rows, in.run, &total) ||
+      __builtin_mul_overflow(total, hs, &hp_b) ||
+      __builtin_mul_overflow(in.run, kind == MX_LOAD ? bits : hs * 8, &run_b))
+    throw std::invalid_argument(who + ": segment size overflows");
+  run_b /= 8;
+  q_b = total / 8 * bits + total % 8 * bits / 8;
+  uint64_t odd = in.run | in.scale_e0 | (in.rows > 1 ? in.scale_pitch : 0);
+  if (fmt == MX_E2M1 && (odd & 1))
+    throw std::invalid_argument(who + ": F4 piece splits a byte");
+  if (kind == MX_SCALES && (odd % MX_BLOCK))
+    throw std::invalid_argument(who + ": not whole blocks of 32");
+  MxSeg g;
+  g.src = in.a; g.dst = in.b; g.rows = in.rows; g.run = in.run;
+  g.src_pitch = in.pitch; g.scale_ptr = in.scale_ptr;
+  g.scale_e0 = in.scale_e0; g.scale_pitch = in.scale_pitch;
+  g.dt = (uint32_t)in.hp_dt; g.fmt = fmt;
+  if (!total) return g;
+  if (!in.scale_ptr) throw std::invalid_argument(who + ": scale_ptr is null");
+  if (__builtin_mul_overflow(in.rows - 1, in.scale_pitch, &last) ||
+      __builtin_add_overflow(last, in.run, &last) ||
+      __builtin_add_overflow(last, in.scale_e0, &last) ||
+      __builtin_add_overflow(in.scale_ptr, last / MX_BLOCK + 1, &end))
+    throw std::invalid_argument(who + ": scale range overflows");
+  if (__builtin_mul_overflow(in.rows - 1, in.pitch, &span) ||
+      __builtin_add_overflow(span, run_b, &span) ||
+      __builtin_add_overflow(in.a, span, &end))
+    throw std::invalid_argument(who + ": source range overflows");
+  if (in.rows > 1 && in.pitch < run_b)
+    throw std::invalid_argument(who + ": rows overlap");
+  if (kind == MX_LOAD) {
+    if (end > cap) throw std::invalid_argument(who + ": arena range out of bounds");
+    if (in.b == 0 || in.b % hs || __builtin_add_overflow(in.b, hp_b, &end))
+      throw std::invalid_argument(who + ": dst_ptr null, misaligned or overflowing");
+  } else {
+    if (in.a == 0 || in.a % ss)
+      throw std::invalid_argument(who + ": src_ptr null or misaligned");
+    if (kind == MX_STORE &&
+        (__builtin_add_overflow(in.b, q_b, &end) || end > cap))
+      throw std::invalid_argument(who + ": arena range out of bounds");
+  }
+  return g;
+}
+
+static MxArgs mx_args(const MxSegTuple& t) {
+  return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t),
+          std::get<4>(t), std::get<5>(t), std::get<6>(t), std::get<7>(t),
+          std::get<8>(t), std::get<9>(t), std::get<10>(t)};
+}
+
+// [first, last) of the E8M0 bytes a validated segment touches
+static std::pair<uint64_t, uint64_t> mx_scale_span(const MxSeg& g) {
+  uint64_t last = g.scale_e0 + (g.rows - 1) * g.scale_pitch + g.run - 1;
+  return {g.scale_ptr + g.scale_e0 / MX_BLOCK,
+          g.scale_ptr + last / MX_BLOCK + 1};
+}
+
+static void mx_check_ranges(int device, const std::string& who, MxKind kind,
+                            const MxSeg& g,
+                            std::vector<std::pair<uint64_t, uint64_t>>& known) {
+  uint64_t hs = cast_itemsize(g.dt);
+  if (kind == MX_LOAD)
+    check_device_range(device, g.dst, g.dst + g.rows * g.run * hs, who,
+                       "dst_ptr", "destination", known);
+  else
+    check_device_range(device, g.src,
+                       g.src + (g.rows - 1) * g.src_pitch + g.run * hs, who,
+                       "src_ptr", "source", known);
+  auto span = mx_scale_span(g);
+  check_device_range(device, span.first, span.second, who, "scale_ptr",
+                     "scales", known);
+}
+
+// Segments: (src_ptr, dst_off, rows, run, src_pitch, src_dtype, dst_dtype,
+// scale_ptr, scale_e0, scale_pitch, 32), F32/F16/BF16 -> F8_E4M3 or F4.
+static void arena_mx_store_ptr(int h, std::vector<MxSegTuple> segs_in) {
+  Arena* a = get_arena(h);
+  std::vector<MxSeg> segs;
+  segs.reserve(segs_in.size());
+  for (auto& t : segs_in) {
+    MxSeg g = mx_validate("mx store", MX_STORE, a->cap, mx_args(t));
+    if (g.rows * g.run) segs.push_back(g);
+  }
+  if (segs.empty()) return;
+  py::gil_scoped_release rel;
+  if (!a->is_dev()) {
+    for (auto& g : segs)
+      mx_store_segment_host((const uint8_t*)g.src, (uint8_t*)a->base + g.dst, g);
+    return;
+  }
+  Tiles tiles = build_tiles(
+      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
+      [](size_t) { return (uint64_t)CAST_TILE; }, "mx store");
+  std::lock_guard<std::mutex> g(a->mu);
+  HIP_CHECK(hipSetDevice(a->device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  for (auto& s : segs) mx_check_ranges(a->device, "mx store", MX_STORE, s, known);
+  Scratch sc(a, tiles.room<MxSeg>(segs.size()));
+  DevTiles<MxSeg> d = upload_tiles(a, sc, segs, tiles);
+  launch(mx_store_kernel, d.grid(), WG, a->kstream, (uint8_t*)a->base, d.items,
+         d.tile_item, d.tile_off, d.n_tiles);
+  // the sources are the caller's to free or overwrite once this returns
+  HIP_CHECK(hipStreamSynchronize(a->kstream));
+}
+
+// Segments: (src_off, dst_ptr, rows, run, src_pitch, src_dtype, dst_dtype,
+// scale_ptr, scale_e0, scale_pitch, 32), F8_E4M3 or F4 -> F32/F16/BF16.
+static void arena_mx_convert_ptr(int h, std::vector<MxSegTuple> segs_in) {
+  Arena* a = get_arena(h);
+  std::vector<MxSeg> segs;
+  segs.reserve(segs_in.size());
+  for (auto& t : segs_in) {
+    MxArgs in = mx_args(t);
+    std::swap(in.hp_dt, in.stored_dt);     // the tuple is (src, dst) ordered
+    MxSeg g = mx_validate("mx convert", MX_LOAD, a->cap, in);
+    if (g.rows * g.run) segs.push_back(g);
+  }
+  if (segs.empty()) return;
+  py::gil_scoped_release rel;
+  if (!a->is_dev()) {
+    for (auto& g : segs)
+      mx_load_segment_host((const uint8_t*)a->base + g.src, (uint8_t*)g.dst, g);
+    return;
+  }
+  Tiles tiles = build_tiles(
+      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
+      [](size_t) { return (uint64_t)CAST_TILE; }, "mx convert");
+  std::lock_guard<std::mutex> g(a->mu);
+  HIP_CHECK(hipSetDevice(a->device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  for (auto& s : segs) mx_check_ranges(a->device, "mx convert", MX_LOAD, s, known);
+  Scratch sc(a, tiles.room<MxSeg>(segs.size()));
+  DevTiles<MxSeg> d = upload_tiles(a, sc, segs, tiles);
+  launch(mx_load_kernel, d.grid(), WG, a->kstream, (const uint8_t*)a->base,
+         d.items, d.tile_item, d.tile_off, d.n_tiles);
+  HIP_CHECK(hipStreamSynchronize(a->kstream));
+}
+
+// Segments: (src_ptr, rows, run, src_pitch, src_dtype, stored_dtype,
+// out_ptr): the E8M0 bytes of a whole tensor of rows * run elements (run a
+// multiple of 32) land at out_ptr[0 : rows * run / 32].  device >= 0: one
+// mx_scales_kernel launch on the caller's thread stream; -1: the host loop.
+typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                   uint64_t> MxScaleTuple;
+
+static void mx_scales(int device, std::vector<MxScaleTuple> segs_in) {
+  if (device < -1) throw std::invalid_argument("mx scales: bad device");
+  std::vector<MxSeg> segs;
+  segs.reserve(segs_in.size());
+  for (auto& t : segs_in) {
+    MxArgs in{std::get<0>(t), 0, std::get<1>(t), std::get<2>(t),
+              std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
+              0, std::get<2>(t), MX_BLOCK};
+    MxSeg g = mx_validate("mx scales", MX_SCALES, 0, in);
+    if (g.rows * g.run) segs.push_back(g);
+  }
+  if (segs.empty()) return;
+  py::gil_scoped_release rel;
+  if (device < 0) {
+    for (auto& g : segs) mx_scales_segment_host(g);
+    return;
+  }
+  Tiles tiles = build_tiles(
+      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
+      [](size_t) { return (uint64_t)CAST_TILE; }, "mx scales");
+  HIP_CHECK(hipSetDevice(device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  for (auto& s : segs) mx_check_ranges(device, "mx scales", MX_SCALES, s, known);
+  hipStream_t s = thread_stream(device);
+  size_t room = tiles.room<MxSeg>(segs.size());
+  DevFree mem;
+  HIP_CHECK(hipMalloc(&mem.p, room));
+  Scratch sc(mem.p, room);
+  DevTiles<MxSeg> d = upload_tiles(s, sc, segs, tiles);
+  launch(mx_scales_kernel, d.grid(), WG, s, d.items, d.tile_item, d.tile_off,
+         d.n_tiles);
+  // the scales are read and the tables freed once this returns
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// host conversion of `n` packed elements under the E8M0 bytes in `scales`,
+// element i using scales[(scale_e0 + i) / 32]: quantising when dst_dtype is
+// F8_E4M3 / F4, dequantising when src_dtype is (the byte paths)
+static py::bytes mx_convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
+                                 uint64_t n, py::buffer scales,
+                                 uint64_t scale_e0) {
+  py::buffer_info bi = src.request(), sbi = scales.request();
+  bool quant = sdt <= DT_BF16;
+  MxArgs in{0, 0, 1, n, 0, quant ? sdt : ddt, quant ? ddt : sdt,
+            (uint64_t)(uintptr_t)sbi.ptr, scale_e0, n, MX_BLOCK};
+  uint64_t have = (uint64_t)bi.size * bi.itemsize;
+  std::vector<uint64_t> out;
+  MxSeg g;
+  if (quant) {
+    in.a = (uint64_t)(uintptr_t)bi.ptr;
+    g = mx_validate("mx convert", MX_STORE, ~0ull, in);
+    if (n > have / cast_itemsize(g.dt))
+      throw std::invalid_argument("mx convert: source shorter than n");
+  } else {
+    // a load from a one-row "arena" that is the source buffer; the
+    // destination is this call's own
+    in.b = 8;
+    g = mx_validate("mx convert", MX_LOAD, have, in);
+  }
+  uint64_t last;
+  if (n && (__builtin_add_overflow(scale_e0, n - 1, &last) || !sbi.ptr ||
+            last / MX_BLOCK >= (uint64_t)sbi.size * sbi.itemsize))
+    throw std::invalid_argument("mx convert: scales shorter than the blocks");
+  uint64_t out_b = quant ? n * mx_bits(g.fmt) / 8 : n * cast_itemsize(g.dt);
+  if (out_b > (1ull << 40))
+    throw std::invalid_argument("mx convert: segment size overflows");
+  out.resize(out_b / 8 + 1);
+  if (n) {
+    if (quant)
+      mx_store_segment_host((const uint8_t*)bi.ptr, (uint8_t*)out.data(), g);
+    else
+      mx_load_segment_host((const uint8_t*)bi.ptr, (uint8_t*)out.data(), g);
+  }
+  return py::bytes((const char*)out.data(), out_b);
+}
+
 static uintptr_t arena_base_ptr(int h) {
   return (uintptr_t)get_arena(h)->base;
 }
@@ -2140,6 +2395,10 @@ PYBIND11_MODULE(_native, m) {
         py::arg("dst_dtype"), py::arg("n"), py::arg("scales") = py::none(),
         py::arg("scale_every") = 0, py::arg("scale_e0") = 0);
   m.def("absmax_scales", &absmax_scales);
+  m.def("arena_mx_store_ptr", &arena_mx_store_ptr);
+  m.def("arena_mx_convert_ptr", &arena_mx_convert_ptr);
+  m.def("mx_scales", &mx_scales);
+  m.def("mx_convert_host", &mx_convert_host);
   m.def("arena_base_ptr", &arena_base_ptr);
   m.def("arena_read_batch", &arena_read_batch);
   m.def("reader_register", &reader_register);

@@ -290,10 +290,17 @@ class SyncLocalReader:
         dequantising load of Arena.convert_ptr: every piece it is cut into
         carries the dense index it starts at, so each element keeps its
         own group's scale; its segments and slow entries are then 10 and 8
-        fields long."""
+        fields long.
+
+        An MX request appends (scale_ptr, scale_e0, scale_pitch, 32)
+        instead: F8_E4M3 or F4 elements (`run` counts elements, two per
+        byte for F4) under E8M0 block scales, scale_e0 the tensor index of
+        the request's first element and scale_pitch the tensor elements
+        between its runs.  Its pieces carry the tensor index THEY start
+        at, which follows from where they start in the file."""
         import bisect
 
-        from curvine_amd.native import DTYPE_ITEMSIZE, DTYPES
+        from curvine_amd.native import DTYPE_BITS, DTYPES
         groups: dict[int, tuple[object, list]] = {}
         slow: list[tuple[int, int, str, str, int]] = []
         blocks = self.fb.blocks
@@ -310,14 +317,18 @@ class SyncLocalReader:
         for off, rows, run, pitch, sdt, ddt, dptr, *scale in requests:
             if rows <= 0 or run <= 0:
                 continue
-            ss, ds = DTYPE_ITEMSIZE[sdt], DTYPE_ITEMSIZE[ddt]
+            sbits, ds = DTYPE_BITS[sdt], DTYPE_BITS[ddt] // 8
             sc, dc = DTYPES[sdt], DTYPES[ddt]
-            run_b = run * ss
+            run_b = run * sbits // 8
 
-            def scaled_at(dst):
-                """The scale fields of a piece that lands at dst."""
+            def scaled_at(dst, pos):
+                """The scale fields of a piece that lands at dst and
+                starts at file offset pos."""
                 if not scale:
                     return ()
+                if len(scale) == 4:
+                    sptr, e0, spitch, blk = scale
+                    return (sptr, e0 + (pos - off) * 8 // sbits, spitch, blk)
                 sptr, every, e0 = scale
                 return (sptr, every, e0 + (dst - dptr) // ds)
 
@@ -332,12 +343,12 @@ class SyncLocalReader:
                     _, segs = groups.setdefault(arena.handle, (arena, []))
                     segs.append((r.meta["offset"] + pos - blocks[idx].offset,
                                  dst, n_rows, n_run, pitch, sc, dc)
-                                + scaled_at(dst))
+                                + scaled_at(dst, pos))
                 else:
                     for k in range(n_rows):
                         d_k = dst + k * n_run * ds
                         slow.append((pos + k * pitch, n_run, sdt, ddt, d_k)
-                                    + scaled_at(d_k))
+                                    + scaled_at(d_k, pos + k * pitch))
 
             r_i = 0
             while r_i < rows:
@@ -358,17 +369,17 @@ class SyncLocalReader:
                 # split on whole elements
                 e = 0
                 while e < run:
-                    p = pos + e * ss
+                    p = pos + e * sbits // 8
                     idx = block_at(p)
                     if idx is None:       # hole: pread synthesizes zeros
                         slow.append((p, run - e, sdt, ddt, dst + e * ds)
-                                    + scaled_at(dst + e * ds))
+                                    + scaled_at(dst + e * ds, p))
                         break
                     avail = blocks[idx].offset + blocks[idx].block.length - p
-                    k = min(run - e, avail // ss)
+                    k = min(run - e, avail * 8 // sbits)
                     if k == 0:            # element straddles two blocks
                         slow.append((p, 1, sdt, ddt, dst + e * ds)
-                                    + scaled_at(dst + e * ds))
+                                    + scaled_at(dst + e * ds, p))
                         e += 1
                         continue
                     emit(idx, p, 1, k, dst + e * ds)
@@ -386,6 +397,26 @@ class SyncLocalReader:
         for arena, segs in groups:
             arena.convert_ptr(segs)
         for off, n, sdt, ddt, dptr, *scale in slow:
+            nbytes = n * native.DTYPE_BITS[sdt] // 8
+            if len(scale) == 4:
+                # the E8M0 bytes of the blocks this extent touches
+                sptr, e0, _spitch, blk = scale
+                g0, g1 = e0 // blk, (e0 + n - 1) // blk
+                sbuf = (ctypes.c_uint8 * (g1 - g0 + 1))()
+                if dst_on_device:
+                    native.load().memcpy_d2h(ctypes.addressof(sbuf),
+                                             sptr + g0, len(sbuf))
+                else:
+                    ctypes.memmove(sbuf, sptr + g0, len(sbuf))
+                raw = self.pread(off, nbytes)
+                if len(raw) != nbytes:
+                    raise err.OutOfRange(
+                        f"typed read at {off}: short read ({len(raw)} bytes)")
+                out = native.mx_convert_host(
+                    raw, native.DTYPES[sdt], native.DTYPES[ddt], n, sbuf,
+                    e0 - g0 * blk)
+                self._land(out, dptr, dst_on_device)
+                continue
             kw = {}
             if scale:
                 # the groups this extent touches, fetched to the host
@@ -400,18 +431,24 @@ class SyncLocalReader:
                     ctypes.memmove(sbuf, sptr + 4 * g0, 4 * len(sbuf))
                 kw = {"scales": sbuf, "scale_every": every,
                       "scale_e0": e0 - g0 * every}
-            raw = self.pread(off, n * native.DTYPE_ITEMSIZE[sdt])
-            if len(raw) != n * native.DTYPE_ITEMSIZE[sdt]:
+            raw = self.pread(off, nbytes)
+            if len(raw) != nbytes:
                 raise err.OutOfRange(
                     f"typed read at {off}: short read ({len(raw)} bytes)")
             out = native.convert_host(raw, native.DTYPES[sdt],
                                       native.DTYPES[ddt], n, **kw)
-            if dst_on_device:
-                buf = (ctypes.c_char * len(out)).from_buffer_copy(out)
-                native.load().memcpy_h2d(dptr, ctypes.addressof(buf),
-                                         len(out))
-            else:
-                ctypes.memmove(dptr, out, len(out))
+            self._land(out, dptr, dst_on_device)
+
+    @staticmethod
+    def _land(out: bytes, dptr: int, dst_on_device: bool) -> None:
+        import ctypes
+
+        from curvine_amd import native
+        if dst_on_device:
+            buf = (ctypes.c_char * len(out)).from_buffer_copy(out)
+            native.load().memcpy_h2d(dptr, ctypes.addressof(buf), len(out))
+        else:
+            ctypes.memmove(dptr, out, len(out))
 
     def verify(self) -> list[int]:
         """Recompute every resident block's CRC32C (HBM: device kernel)

@@ -18,6 +18,12 @@ A source stored as F8_E4M3 carries the f32 scales of its groups
 element of the tensor it starts at, so a tensor cut by a block boundary
 keeps dividing every row by that row's scale, and the byte path hands the
 same scales to `convert_host`.
+
+An MX source (`mx`: stored as F8_E4M3 or F4 under E8M0 block scales, one
+byte per 32 elements at `scale_ptr`) is carried the same way: each piece
+names the dense element it starts at, which may be mid-block, and the byte
+path hands the scale bytes to `mx_convert_host`.  F4 packs two elements
+per byte, so sizes here are counted in bits.
 """
 from __future__ import annotations
 
@@ -30,7 +36,8 @@ from curvine_amd.client.block_client import (BlockWriterLocal,
                                              make_block_writer)
 from curvine_amd.client.fs_client import FsClient
 from curvine_amd.model import FileStatus
-from curvine_amd.native import (DTYPE_ITEMSIZE, DTYPES, convert_supported,
+from curvine_amd.native import (DTYPE_BITS, DTYPE_ITEMSIZE, DTYPES, MX_BLOCK,
+                                convert_supported, mx_quantize_supported,
                                 quantize_supported)
 
 
@@ -45,7 +52,12 @@ class TypedSource:
     Stored as F8_E4M3 the source is quantised: `scale_ptr` is the address
     (on the source's side) of the f32 scales of its tensor, dense element e
     using scale e // `scale_every` (0: one scale), and `scales_host()`
-    returns the same scales as a host buffer (the byte path)."""
+    returns the same scales as a host buffer (the byte path).
+
+    `mx`: stored as F8_E4M3 or F4, `scale_ptr` the address of the tensor's
+    E8M0 bytes, dense element e using byte e // 32; `scales_host()` as
+    above.  The dense tensor's rows end on a block boundary, so `run` is a
+    multiple of 32 wherever there is more than one row."""
     file_off: int
     ptr: int
     rows: int
@@ -58,6 +70,7 @@ class TypedSource:
     scale_ptr: int = 0
     scale_every: int = 0
     scales_host: Callable[[], object] | None = None
+    mx: bool = False
 
     @property
     def scaled(self) -> bool:
@@ -69,7 +82,7 @@ class TypedSource:
 
     @property
     def nbytes(self) -> int:
-        return self.numel * DTYPE_ITEMSIZE[self.dst_dt]
+        return self.numel * DTYPE_BITS[self.dst_dt] // 8
 
     def pieces(self, e0: int, e1: int):
         """(ptr, rows, run) of dense elements [e0, e1): at most a partial
@@ -106,7 +119,16 @@ def validate_layout(header: bytes, sources: list[TypedSource],
         if s.src_dt not in DTYPES or s.dst_dt not in DTYPES:
             raise err.InvalidArgument(
                 f"typed write: unknown dtype {s.src_dt!r}/{s.dst_dt!r}")
-        if s.scaled:
+        if s.mx:
+            if not mx_quantize_supported(s.src_dt, s.dst_dt):
+                raise err.Unsupported(
+                    f"typed write: no MX store of {s.src_dt} as {s.dst_dt}")
+            if not s.scale_ptr or s.scales_host is None or \
+                    s.numel % MX_BLOCK or (s.rows > 1 and s.run % MX_BLOCK):
+                raise err.InvalidArgument(
+                    "typed write: MX source without scales or not in "
+                    "blocks of 32")
+        elif s.scaled:
             if s.dst_dt != "F8_E4M3" or not quantize_supported(s.src_dt):
                 raise err.Unsupported(
                     f"typed write: no scaled store of {s.src_dt} as "
@@ -117,7 +139,8 @@ def validate_layout(header: bytes, sources: list[TypedSource],
         elif not convert_supported(s.src_dt, s.dst_dt):
             raise err.Unsupported(
                 f"typed write: cannot store {s.src_dt} as {s.dst_dt}")
-        ss, ds = DTYPE_ITEMSIZE[s.src_dt], DTYPE_ITEMSIZE[s.dst_dt]
+        ss = DTYPE_ITEMSIZE[s.src_dt]
+        ds = max(1, DTYPE_BITS[s.dst_dt] // 8)
         if s.rows <= 0 or s.run <= 0 or s.ptr <= 0 or s.ptr % ss:
             raise err.InvalidArgument(
                 "typed write: empty, null or misaligned source")
@@ -158,9 +181,9 @@ class TypedFileWriter:
         for s in self.sources:
             lo, hi = max(b0, s.file_off), min(b1, s.file_off + s.nbytes)
             if lo < hi:
-                ds = DTYPE_ITEMSIZE[s.dst_dt]
-                parts.append((s, lo - b0, (lo - s.file_off) // ds,
-                              (hi - s.file_off) // ds))
+                bits = DTYPE_BITS[s.dst_dt]
+                parts.append((s, lo - b0, (lo - s.file_off) * 8 // bits,
+                              (hi - s.file_off) * 8 // bits))
         return head, parts
 
     def _typed_target(self, parts) -> bool:
@@ -179,15 +202,17 @@ class TypedFileWriter:
     def _typed_pieces(parts):
         pieces = []
         for s, off, e0, e1 in parts:
-            ds = DTYPE_ITEMSIZE[s.dst_dt]
+            bits = DTYPE_BITS[s.dst_dt]
             e = e0                    # the piece's first dense element
             for ptr, rows, run in s.pieces(e0, e1):
                 piece = (off, ptr, rows, run, s.pitch,
                          DTYPES[s.src_dt], DTYPES[s.dst_dt])
-                if s.scaled:
+                if s.mx:              # the dense side is the tensor
+                    piece += (s.scale_ptr, e, run, MX_BLOCK)
+                elif s.scaled:
                     piece += (s.scale_ptr, s.scale_every, e)
                 pieces.append(piece)
-                off += rows * run * ds
+                off += rows * run * bits // 8
                 e += rows * run
         return pieces
 
@@ -198,7 +223,11 @@ class TypedFileWriter:
         buf = bytearray(n)
         for s, off, e0, e1 in parts:
             raw = s.read_host(e0, e1)
-            if s.scaled:
+            if s.mx:
+                raw = native.mx_convert_host(
+                    raw, DTYPES[s.src_dt], DTYPES[s.dst_dt], e1 - e0,
+                    s.scales_host(), e0)
+            elif s.scaled:
                 raw = native.convert_host(
                     raw, DTYPES[s.src_dt], DTYPES[s.dst_dt], e1 - e0,
                     scales=s.scales_host(), scale_every=s.scale_every,
@@ -207,7 +236,7 @@ class TypedFileWriter:
                 raw = native.convert_host(raw, DTYPES[s.src_dt],
                                           DTYPES[s.dst_dt], e1 - e0)
             raw = memoryview(raw).cast("B")
-            n_b = (e1 - e0) * DTYPE_ITEMSIZE[s.dst_dt]
+            n_b = (e1 - e0) * DTYPE_BITS[s.dst_dt] // 8
             if len(raw) != n_b:
                 raise err.FsError(
                     f"typed write: source gave {len(raw)} bytes for {n_b}")

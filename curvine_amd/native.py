@@ -152,8 +152,19 @@ class Arena:
         A 10-tuple appends (scale_ptr, scale_every, scale_e0) and
         dequantises F8_E4M3 -> F32/F16/BF16: dense element e is multiplied
         by the f32 scale at scale_ptr[(scale_e0 + e) // scale_every]
-        (scale_every 0: one scale), memory on the destinations' side."""
-        self._n.arena_convert_ptr(self.handle, segments)
+        (scale_every 0: one scale), memory on the destinations' side.
+
+        An 11-tuple appends (scale_ptr, scale_e0, scale_pitch, 32) and
+        dequantises an MX tensor, F8_E4M3 or F4 (two per byte, `run` in
+        elements) -> F32/F16/BF16: the element in row r, column c is
+        multiplied by the E8M0 scale byte at
+        scale_ptr[(scale_e0 + r * scale_pitch + c) // 32], one
+        mx_load_kernel launch for all of them."""
+        plain, mx = _split_mx(segments)
+        if plain:
+            self._n.arena_convert_ptr(self.handle, plain)
+        if mx:
+            self._n.arena_mx_convert_ptr(self.handle, mx)
 
     def store_ptr(self, segments: list[tuple]) -> None:
         """Typed store, the scatter direction of convert_ptr: each segment
@@ -171,8 +182,17 @@ class Arena:
         F32/F16/BF16 -> F8_E4M3: dense element e is divided by the f32
         scale at scale_ptr[(scale_e0 + e) // scale_every] (scale_every 0:
         one scale; see absmax_scales) and cast saturating.  Quantising
-        without a scale_ptr is refused."""
-        self._n.arena_store_ptr(self.handle, segments)
+        without a scale_ptr is refused.
+
+        An 11-tuple appends (scale_ptr, scale_e0, scale_pitch, 32) and
+        quantises F32/F16/BF16 -> F8_E4M3 or F4 under the E8M0 block
+        scales of mx_scales, as in convert_ptr: one mx_store_kernel launch
+        for all of them."""
+        plain, mx = _split_mx(segments)
+        if plain:
+            self._n.arena_store_ptr(self.handle, plain)
+        if mx:
+            self._n.arena_mx_store_ptr(self.handle, mx)
 
     def lz4_compress(self, off: int, n: int) -> bytes:
         """Compress arena bytes [off, off+n) into a CVLZ container (HIP
@@ -214,6 +234,13 @@ class Arena:
             self.close()
         except Exception:
             pass
+
+
+def _split_mx(segments):
+    """(7- and 10-tuples, 11-tuples): the MX segments have kernels of
+    their own."""
+    plain = [s for s in segments if len(s) != 11]
+    return plain, [s for s in segments if len(s) == 11]
 
 
 def hip_pool_stats() -> dict:
@@ -258,10 +285,16 @@ class PinnedBuffer:
 # dtype name (safetensors spelling) -> code understood by convert_ptr
 DTYPES = {"F32": 0, "F16": 1, "BF16": 2, "F8_E4M3": 3, "F8_E5M2": 4,
           "F64": 5, "I64": 6, "I32": 7, "I16": 8, "I8": 9, "U8": 10,
-          "BOOL": 11, "U16": 12, "U32": 13, "U64": 14}
+          "BOOL": 11, "U16": 12, "U32": 13, "U64": 14,
+          # the MX dtypes: known to the mx_* entry points only (code 15 and
+          # these stay refused by convert_ptr / store_ptr / convert_host)
+          "F8_E8M0": 16, "F4": 17}
 DTYPE_ITEMSIZE = {"F32": 4, "F16": 2, "BF16": 2, "F8_E4M3": 1, "F8_E5M2": 1,
                   "F64": 8, "I64": 8, "I32": 4, "I16": 2, "I8": 1, "U8": 1,
-                  "BOOL": 1, "U16": 2, "U32": 4, "U64": 8}
+                  "BOOL": 1, "U16": 2, "U32": 4, "U64": 8, "F8_E8M0": 1}
+# bits per stored element: F4 (E2M1, two per byte) has no itemsize
+DTYPE_BITS = {k: 8 * v for k, v in DTYPE_ITEMSIZE.items()}
+DTYPE_BITS["F4"] = 4
 # floating sources the kernel converts, and the targets it converts to
 CONVERT_SOURCES = ("F32", "F16", "BF16", "F8_E4M3", "F8_E5M2")
 CONVERT_TARGETS = ("F32", "F16", "BF16")
@@ -284,6 +317,44 @@ def quantize_supported(src: str) -> bool:
 def dequantize_supported(dst: str) -> bool:
     """Scaled F8_E4M3 can be loaded as `dst`."""
     return dst in DEQUANTIZE_TARGETS
+
+
+# the MX pairs: F32/F16/BF16 <-> F8_E4M3 (MXFP8) or F4 (MXFP4), blocks of
+# 32 elements under one E8M0 scale byte
+MX_BLOCK = 32
+MX_ELEMENTS = ("F8_E4M3", "F4")
+
+
+def mx_quantize_supported(src: str, dst: str) -> bool:
+    """`src` can be stored as MX elements `dst`."""
+    return src in QUANTIZE_SOURCES and dst in MX_ELEMENTS
+
+
+def mx_dequantize_supported(src: str, dst: str) -> bool:
+    """MX elements `src` can be loaded as `dst`."""
+    return src in MX_ELEMENTS and dst in DEQUANTIZE_TARGETS
+
+
+def mx_scales(device: int, segments: list[tuple]) -> None:
+    """E8M0 block scales of whole tensors.  Each segment is (src_ptr,
+    rows, run, src_pitch, src_dtype, stored_dtype, out_ptr): `rows` runs of
+    `run` F32/F16/BF16 elements (`run` a multiple of 32), `src_pitch` bytes
+    apart; out_ptr[0 : rows * run // 32] receives one byte per block of 32,
+    max(E - emax, 0) with E the biased f32 exponent of the block's largest
+    finite |x| and emax 8 for F8_E4M3, 2 for F4.  device >= 0: one
+    mx_scales_kernel launch for the whole list, synchronised on return;
+    -1: the same routine in C++ over host memory.  Bad arguments raise
+    ValueError before anything runs."""
+    load().mx_scales(device, segments)
+
+
+def mx_convert_host(buf, src_dtype: int, dst_dtype: int, n: int, scales,
+                    scale_e0: int = 0) -> bytes:
+    """Quantise (F32/F16/BF16 -> F8_E4M3 / F4) or dequantise (the reverse)
+    `n` packed elements on the host with the kernels' own routines;
+    element i uses the E8M0 byte scales[(scale_e0 + i) // 32]."""
+    return load().mx_convert_host(buf, src_dtype, dst_dtype, n, scales,
+                                  scale_e0)
 
 
 def convert_host(buf, src_dtype: int, dst_dtype: int, n: int, scales=None,

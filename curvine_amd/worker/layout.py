@@ -73,14 +73,15 @@ class BlockWriter:
         reservation is refused before anything is written.  Layouts that
         cannot take a pointer raise Unsupported: the caller then writes
         bytes.  A piece may append (scale_ptr, scale_every, scale_e0): the
-        quantising store of Arena.store_ptr.  Returns the bytes written."""
-        from curvine_amd.native import DTYPE_ITEMSIZE, DTYPES
-        isz = {DTYPES[k]: v for k, v in DTYPE_ITEMSIZE.items()}
+        quantising store of Arena.store_ptr, or (scale_ptr, scale_e0,
+        scale_pitch, 32), its MX store.  Returns the bytes written."""
+        from curvine_amd.native import DTYPE_BITS, DTYPES
+        bits = {DTYPES[k]: v for k, v in DTYPE_BITS.items()}
         total, top = 0, self.pos
         for off, _ptr, rows, run, _pitch, _sdt, ddt, *_scale in pieces:
-            if ddt not in isz:
+            if ddt not in bits:
                 raise err.InvalidArgument(f"store: unknown dtype code {ddt}")
-            n = rows * run * isz[ddt]
+            n = rows * run * bits[ddt] // 8
             if off < 0 or off + n > self.meta["reserved"]:
                 raise err.InvalidArgument(
                     f"typed piece of {n} bytes at {off} passes the block's "
