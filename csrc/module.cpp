@@ -152,6 +152,7 @@ static uint32_t crc32c_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
 #include "lz4.hip"
 #include "tensor_cast.hip"
 #include "mx_cast.hip"
+#include "block_cast.hip"
 
 // ---------------------------------------------------------------------------
 // GPU availability
@@ -1365,6 +1366,23 @@ struct DevFree {
   ~DevFree() { if (p) (void)hipFree(p); }
 };
 
+// each slot is zeroed and finished once, however the segments share them
+static std::vector<ScaleSlots> merge_scale_slots(std::vector<ScaleSlots> slots) {
+  std::sort(slots.begin(), slots.end(),
+            [](const ScaleSlots& x, const ScaleSlots& y) { return x.ptr < y.ptr; });
+  std::vector<ScaleSlots> merged;
+  for (auto& r : slots) {
+    if (!merged.empty() && r.ptr <= merged.back().ptr + merged.back().n * 4) {
+      uint64_t end = std::max(merged.back().ptr + merged.back().n * 4,
+                              r.ptr + r.n * 4);
+      merged.back().n = (end - merged.back().ptr) / 4;
+    } else {
+      merged.push_back(r);
+    }
+  }
+  return merged;
+}
+
 static void absmax_scales(int device, std::vector<AbsmaxSegTuple> segs_in) {
   if (device < -1) throw std::invalid_argument("absmax: bad device");
   std::vector<AbsmaxSeg> segs;
@@ -1405,19 +1423,7 @@ static void absmax_scales(int device, std::vector<AbsmaxSegTuple> segs_in) {
     slots.push_back({out, n_groups});
   }
   if (slots.empty()) return;
-  // each slot is zeroed and finished once, however the segments share them
-  std::sort(slots.begin(), slots.end(),
-            [](const ScaleSlots& x, const ScaleSlots& y) { return x.ptr < y.ptr; });
-  std::vector<ScaleSlots> merged;
-  for (auto& r : slots) {
-    if (!merged.empty() && r.ptr <= merged.back().ptr + merged.back().n * 4) {
-      uint64_t end = std::max(merged.back().ptr + merged.back().n * 4,
-                              r.ptr + r.n * 4);
-      merged.back().n = (end - merged.back().ptr) / 4;
-    } else {
-      merged.push_back(r);
-    }
-  }
+  std::vector<ScaleSlots> merged = merge_scale_slots(std::move(slots));
   py::gil_scoped_release rel;
   if (device < 0) {
     for (auto& r : merged) scale_slots_host(r, false);
@@ -1712,6 +1718,314 @@ static py::bytes mx_convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
       mx_store_segment_host((const uint8_t*)bi.ptr, (uint8_t*)out.data(), g);
     else
       mx_load_segment_host((const uint8_t*)bi.ptr, (uint8_t*)out.data(), g);
+  }
+  return py::bytes((const char*)out.data(), out_b);
+}
+
+// ---- 2-D block scales: one F32 scale per bm x bn tile (block_cast.hip) ----
+//
+// Entry points of their own, as the MX ones.  A segment names its
+// high-precision side (F32/F16/BF16) and F8_E4M3 and carries (scale_ptr,
+// scale_e0, scale_pitch, M, K, bm, bn): the element in row r, column c is
+// element t = scale_e0 + r * scale_pitch + c of a tensor (..., M, K) and
+// uses the f32 scale of its tile, block_scale_index(t).  Every argument
+// error is raised on the host before any launch.
+
+enum BlockKind { BLOCK_ABSMAX, BLOCK_STORE, BLOCK_LOAD };
+
+struct BlockArgs {
+  uint64_t a, b, rows, run, pitch, hp_dt, stored_dt, scale_ptr, scale_e0,
+      scale_pitch, M, K, bm, bn;
+};
+
+typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                   uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                   uint64_t, uint64_t> BlockSegTuple;
+
+// [first, last] of the scale indices a segment with elements can meet:
+// the first tile of its first element's row .. the last of its last one's
+static std::pair<uint64_t, uint64_t> block_scale_range(const BlockSeg& g) {
+  uint64_t left;
+  uint64_t tb = g.scale_e0 + (g.rows - 1) * g.scale_pitch + g.run - 1;
+  return {block_scale_index(g, g.scale_e0 / g.K * g.K, left),
+          block_scale_index(g, tb / g.K * g.K + g.K - 1, left)};
+}
+
+// kind BLOCK_ABSMAX / BLOCK_STORE: a = absolute source; BLOCK_STORE: b =
+// arena offset; BLOCK_LOAD: a = arena offset, b = absolute destination.
+// n_scales: how many scales scale_ptr holds, 0 = not known here.
+static BlockSeg block_validate(const std::string& who, BlockKind kind,
+                               uint64_t cap, const BlockArgs& in,
+                               uint64_t n_scales = 0) {
+  if (in.hp_dt > DT_BF16)
+    throw std::invalid_argument(who + ": not F32/F16/BF16 on the wide side");
+  if (in.stored_dt != DT_F8_E4M3)
+    throw std::invalid_argument(who + ": stored dtype is not F8_E4M3");
+  if (!in.M || !in.K || !in.bm || !in.bn)
+    throw std::invalid_argument(who + ": M, K, bm and bn must be positive");
+  uint64_t hs = cast_itemsize((uint32_t)in.hp_dt);
+  uint64_t ss = kind == BLOCK_LOAD ? 1 : hs;         // source itemsize
+  uint64_t total, run_b, hp_b, span, end, last;
+  if (__builtin_mul_overflow(in.rows, in.run, &total) ||
+      __builtin_mul_overflow(total, hs, &hp_b) ||
+      __builtin_mul_overflow(in.run, ss, &run_b))
+    throw std::invalid_argument(who + ": segment size overflows");
+  BlockSeg g;
+  g.src = in.a; g.dst = in.b; g.rows = in.rows; g.run = in.run;
+  g.src_pitch = in.pitch; g.scale_ptr = in.scale_ptr;
+  g.scale_e0 = in.scale_e0; g.scale_pitch = in.scale_pitch;
+  g.M = in.M; g.K = in.K; g.bm = in.bm; g.bn = in.bn;
+  g.tm = (in.M - 1) / in.bm + 1; g.tn = (in.K - 1) / in.bn + 1;
+  g.dt = (uint32_t)in.hp_dt; g.pad = 0;
+  if (!total) return g;
+  if (!in.scale_ptr || in.scale_ptr % 4)
+    throw std::invalid_argument(who + ": scale_ptr null or misaligned");
+  if (in.rows > 1 && in.scale_pitch < in.run)
+    throw std::invalid_argument(who + ": rows overlap in the tensor");
+  uint64_t per_mat, n_mat, hi_b;
+  if (__builtin_mul_overflow(in.rows - 1, in.scale_pitch, &last) ||
+      __builtin_add_overflow(last, in.run, &last) ||
+      __builtin_add_overflow(last, in.scale_e0, &last) ||
+      __builtin_add_overflow(last, in.K, &end) ||
+      __builtin_mul_overflow(g.tm, g.tn, &per_mat) ||
+      __builtin_mul_overflow((last - 1) / in.K / in.M + 1, per_mat, &n_mat) ||
+      __builtin_mul_overflow(n_mat, (uint64_t)4, &hi_b) ||
+      __builtin_add_overflow(in.scale_ptr, hi_b, &end))
+    throw std::invalid_argument(who + ": scale range overflows");
+  if (n_scales && block_scale_range(g).second >= n_scales)
+    throw std::invalid_argument(who + ": tiles pass the scales given");
+  if (__builtin_mul_overflow(in.rows - 1, in.pitch, &span) ||
+      __builtin_add_overflow(span, run_b, &span) ||
+      __builtin_add_overflow(in.a, span, &end))
+    throw std::invalid_argument(who + ": source range overflows");
+  if (in.rows > 1 && (in.pitch < run_b || in.pitch % ss))
+    throw std::invalid_argument(who + ": rows overlap or pitch misaligned");
+  if (kind == BLOCK_LOAD) {
+    if (end > cap) throw std::invalid_argument(who + ": arena range out of bounds");
+    if (in.b == 0 || in.b % hs || __builtin_add_overflow(in.b, hp_b, &end))
+      throw std::invalid_argument(who + ": dst_ptr null, misaligned or overflowing");
+  } else {
+    if (in.a == 0 || in.a % ss)
+      throw std::invalid_argument(who + ": src_ptr null or misaligned");
+    if (kind == BLOCK_STORE &&
+        (__builtin_add_overflow(in.b, total, &end) || end > cap))
+      throw std::invalid_argument(who + ": arena range out of bounds");
+  }
+  return g;
+}
+
+static BlockArgs block_args(const BlockSegTuple& t) {
+  return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t),
+          std::get<4>(t), std::get<5>(t), std::get<6>(t), std::get<7>(t),
+          std::get<8>(t), std::get<9>(t), std::get<10>(t), std::get<11>(t),
+          std::get<12>(t), std::get<13>(t)};
+}
+
+static void block_check_ranges(int device, const std::string& who,
+                               BlockKind kind, const BlockSeg& g,
+                               std::vector<std::pair<uint64_t, uint64_t>>& known) {
+  uint64_t hs = cast_itemsize(g.dt);
+  if (kind == BLOCK_LOAD)
+    check_device_range(device, g.dst, g.dst + g.rows * g.run * hs, who,
+                       "dst_ptr", "destination", known);
+  else
+    check_device_range(device, g.src,
+                       g.src + (g.rows - 1) * g.src_pitch + g.run * hs, who,
+                       "src_ptr", "source", known);
+  auto range = block_scale_range(g);
+  check_device_range(device, g.scale_ptr + range.first * 4,
+                     g.scale_ptr + (range.second + 1) * 4, who, "scale_ptr",
+                     "scales", known);
+}
+
+static Tiles block_tiles(const std::vector<BlockSeg>& segs, const char* who) {
+  return build_tiles(
+      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
+      [](size_t) { return (uint64_t)CAST_TILE; }, who);
+}
+
+// Segments: (src_ptr, dst_off, rows, run, src_pitch, src_dtype, dst_dtype,
+// scale_ptr, scale_e0, scale_pitch, M, K, bm, bn), F32/F16/BF16 -> F8_E4M3.
+static void arena_block_store_ptr(int h, std::vector<BlockSegTuple> segs_in) {
+  Arena* a = get_arena(h);
+  std::vector<BlockSeg> segs;
+  segs.reserve(segs_in.size());
+  for (auto& t : segs_in) {
+    BlockSeg g = block_validate("block store", BLOCK_STORE, a->cap,
+                                block_args(t));
+    if (g.rows * g.run) segs.push_back(g);
+  }
+  if (segs.empty()) return;
+  py::gil_scoped_release rel;
+  if (!a->is_dev()) {
+    for (auto& g : segs)
+      block_store_segment_host((const uint8_t*)g.src,
+                               (uint8_t*)a->base + g.dst, g);
+    return;
+  }
+  Tiles tiles = block_tiles(segs, "block store");
+  std::lock_guard<std::mutex> g(a->mu);
+  HIP_CHECK(hipSetDevice(a->device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  for (auto& s : segs)
+    block_check_ranges(a->device, "block store", BLOCK_STORE, s, known);
+  Scratch sc(a, tiles.room<BlockSeg>(segs.size()));
+  DevTiles<BlockSeg> d = upload_tiles(a, sc, segs, tiles);
+  launch(block_store_kernel, d.grid(), WG, a->kstream, (uint8_t*)a->base,
+         d.items, d.tile_item, d.tile_off, d.n_tiles);
+  // the sources are the caller's to free or overwrite once this returns
+  HIP_CHECK(hipStreamSynchronize(a->kstream));
+}
+
+// Segments: (src_off, dst_ptr, rows, run, src_pitch, src_dtype, dst_dtype,
+// scale_ptr, scale_e0, scale_pitch, M, K, bm, bn), F8_E4M3 -> F32/F16/BF16.
+static void arena_block_convert_ptr(int h, std::vector<BlockSegTuple> segs_in) {
+  Arena* a = get_arena(h);
+  std::vector<BlockSeg> segs;
+  segs.reserve(segs_in.size());
+  for (auto& t : segs_in) {
+    BlockArgs in = block_args(t);
+    std::swap(in.hp_dt, in.stored_dt);     // the tuple is (src, dst) ordered
+    BlockSeg g = block_validate("block convert", BLOCK_LOAD, a->cap, in);
+    if (g.rows * g.run) segs.push_back(g);
+  }
+  if (segs.empty()) return;
+  py::gil_scoped_release rel;
+  if (!a->is_dev()) {
+    for (auto& g : segs)
+      block_load_segment_host((const uint8_t*)a->base + g.src,
+                              (uint8_t*)g.dst, g);
+    return;
+  }
+  Tiles tiles = block_tiles(segs, "block convert");
+  std::lock_guard<std::mutex> g(a->mu);
+  HIP_CHECK(hipSetDevice(a->device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  for (auto& s : segs)
+    block_check_ranges(a->device, "block convert", BLOCK_LOAD, s, known);
+  Scratch sc(a, tiles.room<BlockSeg>(segs.size()));
+  DevTiles<BlockSeg> d = upload_tiles(a, sc, segs, tiles);
+  launch(block_load_kernel, d.grid(), WG, a->kstream, (const uint8_t*)a->base,
+         d.items, d.tile_item, d.tile_off, d.n_tiles);
+  HIP_CHECK(hipStreamSynchronize(a->kstream));
+}
+
+// Segments: (src_ptr, rows, run, src_pitch, src_dtype, out_ptr, scale_e0,
+// scale_pitch, M, K, bm, bn, n_slots): out_ptr[0:n_slots] are the f32 tile
+// scales of the segment's tensor; they are zeroed, receive each tile's amax
+// and become max(amax, 2^-40) / 448, as in absmax_scales.  Segments may
+// share slots.  device >= 0: block_absmax_kernel between two
+// scale_slots_kernel launches on the caller's thread stream; -1: the host
+// loops.
+typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                   uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                   uint64_t> BlockAbsmaxTuple;
+
+static void block_absmax_scales(int device,
+                                std::vector<BlockAbsmaxTuple> segs_in) {
+  if (device < -1) throw std::invalid_argument("block absmax: bad device");
+  std::vector<BlockSeg> segs;
+  std::vector<ScaleSlots> slots;
+  segs.reserve(segs_in.size());
+  for (auto& t : segs_in) {
+    BlockArgs in{std::get<0>(t), 0, std::get<1>(t), std::get<2>(t),
+                 std::get<3>(t), std::get<4>(t), DT_F8_E4M3, std::get<5>(t),
+                 std::get<6>(t), std::get<7>(t), std::get<8>(t),
+                 std::get<9>(t), std::get<10>(t), std::get<11>(t)};
+    uint64_t n_slots = std::get<12>(t), out_b, end;
+    if (n_slots == 0 || in.scale_ptr == 0 || in.scale_ptr % 4 ||
+        __builtin_mul_overflow(n_slots, (uint64_t)4, &out_b) ||
+        __builtin_add_overflow(in.scale_ptr, out_b, &end))
+      throw std::invalid_argument(
+          "block absmax: out_ptr null, misaligned, empty or overflowing");
+    BlockSeg g = block_validate("block absmax", BLOCK_ABSMAX, 0, in, n_slots);
+    if (g.rows * g.run) segs.push_back(g);
+    slots.push_back({in.scale_ptr, n_slots});
+  }
+  if (slots.empty()) return;
+  std::vector<ScaleSlots> merged = merge_scale_slots(std::move(slots));
+  py::gil_scoped_release rel;
+  if (device < 0) {
+    for (auto& r : merged) scale_slots_host(r, false);
+    for (auto& g : segs) block_absmax_segment_host(g);
+    for (auto& r : merged) scale_slots_host(r, true);
+    return;
+  }
+  Tiles tiles = block_tiles(segs, "block absmax");
+  HIP_CHECK(hipSetDevice(device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  for (auto& s : segs)
+    block_check_ranges(device, "block absmax", BLOCK_ABSMAX, s, known);
+  for (auto& r : merged)
+    check_device_range(device, r.ptr, r.ptr + r.n * 4, "block absmax",
+                       "out_ptr", "scales", known);
+  hipStream_t s = thread_stream(device);
+  size_t room = tiles.room<BlockSeg>(segs.size()) +
+                Scratch::room<ScaleSlots>(merged.size());
+  DevFree mem;
+  HIP_CHECK(hipMalloc(&mem.p, room));
+  Scratch sc(mem.p, room);
+  ScaleSlots* d_slots = sc.take<ScaleSlots>(merged.size());
+  HIP_CHECK(hipMemcpyAsync(d_slots, merged.data(),
+                           merged.size() * sizeof(ScaleSlots),
+                           hipMemcpyHostToDevice, s));
+  unsigned slot_grid = (unsigned)std::min<size_t>(merged.size(), 8192);
+  launch(scale_slots_kernel, slot_grid, WG, s, (const ScaleSlots*)d_slots,
+         (uint32_t)merged.size(), 0);
+  if (!tiles.empty()) {
+    DevTiles<BlockSeg> d = upload_tiles(s, sc, segs, tiles);
+    launch(block_absmax_kernel, d.grid(), WG, s, d.items, d.tile_item,
+           d.tile_off, d.n_tiles);
+  }
+  launch(scale_slots_kernel, slot_grid, WG, s, (const ScaleSlots*)d_slots,
+         (uint32_t)merged.size(), 1);
+  // the scales are read and the tables freed once this returns
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// host conversion of `n` packed elements, element i being element
+// scale_e0 + i of a tensor (..., M, K) under bm x bn tile scales:
+// quantising when dst_dtype is F8_E4M3, dequantising when src_dtype is (the
+// byte paths).  `scales` holds the tensor's f32 scales from index scale_g0
+// on; it must cover every tile the elements meet.
+static py::bytes block_convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
+                                    uint64_t n, py::buffer scales,
+                                    uint64_t scale_e0, uint64_t M, uint64_t K,
+                                    uint64_t bm, uint64_t bn,
+                                    uint64_t scale_g0) {
+  py::buffer_info bi = src.request(), sbi = scales.request();
+  bool quant = sdt <= DT_BF16;
+  BlockArgs in{0, 0, 1, n, 0, quant ? sdt : ddt, quant ? ddt : sdt,
+               (uint64_t)(uintptr_t)sbi.ptr, scale_e0, n, M, K, bm, bn};
+  uint64_t have = (uint64_t)bi.size * bi.itemsize;
+  BlockSeg g;
+  if (quant) {
+    in.a = (uint64_t)(uintptr_t)bi.ptr;
+    g = block_validate("block convert", BLOCK_STORE, ~0ull, in);
+    if (n > have / cast_itemsize(g.dt))
+      throw std::invalid_argument("block convert: source shorter than n");
+  } else {
+    // a load from a one-row "arena" that is the source buffer; the
+    // destination is this call's own
+    in.b = 8;
+    g = block_validate("block convert", BLOCK_LOAD, have, in);
+  }
+  if (n) {
+    auto range = block_scale_range(g);
+    uint64_t got = (uint64_t)sbi.size * sbi.itemsize / 4;
+    if (range.first < scale_g0 || range.second - scale_g0 >= got)
+      throw std::invalid_argument("block convert: scales do not cover the tiles");
+    g.scale_ptr -= 4 * scale_g0;           // index 0 of the tensor's scales
+  }
+  uint64_t out_b = quant ? n : n * cast_itemsize(g.dt);
+  if (out_b > (1ull << 40))
+    throw std::invalid_argument("block convert: segment size overflows");
+  std::vector<uint64_t> out(out_b / 8 + 1);
+  if (n) {
+    if (quant)
+      block_store_segment_host((const uint8_t*)bi.ptr, (uint8_t*)out.data(), g);
+    else
+      block_load_segment_host((const uint8_t*)bi.ptr, (uint8_t*)out.data(), g);
   }
   return py::bytes((const char*)out.data(), out_b);
 }
@@ -2399,6 +2713,13 @@ PYBIND11_MODULE(_native, m) {
   m.def("arena_mx_convert_ptr", &arena_mx_convert_ptr);
   m.def("mx_scales", &mx_scales);
   m.def("mx_convert_host", &mx_convert_host);
+  m.def("arena_block_store_ptr", &arena_block_store_ptr);
+  m.def("arena_block_convert_ptr", &arena_block_convert_ptr);
+  m.def("block_absmax_scales", &block_absmax_scales);
+  m.def("block_convert_host", &block_convert_host, py::arg("src"),
+        py::arg("src_dtype"), py::arg("dst_dtype"), py::arg("n"),
+        py::arg("scales"), py::arg("scale_e0"), py::arg("M"), py::arg("K"),
+        py::arg("bm"), py::arg("bn"), py::arg("scale_g0") = 0);
   m.def("arena_base_ptr", &arena_base_ptr);
   m.def("arena_read_batch", &arena_read_batch);
   m.def("reader_register", &reader_register);

@@ -297,7 +297,14 @@ class SyncLocalReader:
         byte for F4) under E8M0 block scales, scale_e0 the tensor index of
         the request's first element and scale_pitch the tensor elements
         between its runs.  Its pieces carry the tensor index THEY start
-        at, which follows from where they start in the file."""
+        at, which follows from where they start in the file.
+
+        A block-scaled request appends (scale_ptr, scale_e0, scale_pitch,
+        M, K, bm, bn): F8_E4M3 elements of a tensor (..., M, K) under one
+        f32 scale per bm x bn tile, scale_ptr the whole scale tensor.  Its
+        pieces carry the tensor index they start at in the same way, and
+        every element finds its tile from its own tensor coordinates, so a
+        request may cut rows and tiles anywhere."""
         import bisect
 
         from curvine_amd.native import DTYPE_BITS, DTYPES
@@ -329,6 +336,10 @@ class SyncLocalReader:
                 if len(scale) == 4:
                     sptr, e0, spitch, blk = scale
                     return (sptr, e0 + (pos - off) * 8 // sbits, spitch, blk)
+                if len(scale) == 7:
+                    sptr, e0, spitch, *geom = scale
+                    return (sptr, e0 + (pos - off) * 8 // sbits, spitch,
+                            *geom)
                 sptr, every, e0 = scale
                 return (sptr, every, e0 + (dst - dptr) // ds)
 
@@ -415,6 +426,30 @@ class SyncLocalReader:
                 out = native.mx_convert_host(
                     raw, native.DTYPES[sdt], native.DTYPES[ddt], n, sbuf,
                     e0 - g0 * blk)
+                self._land(out, dptr, dst_on_device)
+                continue
+            if len(scale) == 7:
+                # the tile scales of the tensor rows this extent touches
+                sptr, e0, _spitch, m, k, bm, bn = scale
+                tm, tn = -(-m // bm), -(-k // bn)
+
+                def tile_row(row):
+                    return (row // m * tm + row % m // bm) * tn
+                g0 = tile_row(e0 // k)
+                g1 = tile_row((e0 + n - 1) // k) + tn
+                sbuf = (ctypes.c_float * (g1 - g0))()
+                if dst_on_device:
+                    native.load().memcpy_d2h(ctypes.addressof(sbuf),
+                                             sptr + 4 * g0, 4 * len(sbuf))
+                else:
+                    ctypes.memmove(sbuf, sptr + 4 * g0, 4 * len(sbuf))
+                raw = self.pread(off, nbytes)
+                if len(raw) != nbytes:
+                    raise err.OutOfRange(
+                        f"typed read at {off}: short read ({len(raw)} bytes)")
+                out = native.block_convert_host(
+                    raw, native.DTYPES[sdt], native.DTYPES[ddt], n, sbuf,
+                    e0, m, k, bm, bn, g0)
                 self._land(out, dptr, dst_on_device)
                 continue
             kw = {}

@@ -159,12 +159,22 @@ class Arena:
         elements) -> F32/F16/BF16: the element in row r, column c is
         multiplied by the E8M0 scale byte at
         scale_ptr[(scale_e0 + r * scale_pitch + c) // 32], one
-        mx_load_kernel launch for all of them."""
-        plain, mx = _split_mx(segments)
+        mx_load_kernel launch for all of them.
+
+        A 14-tuple appends (scale_ptr, scale_e0, scale_pitch, M, K, bm,
+        bn) and dequantises a block-scaled F8_E4M3 tensor (..., M, K) ->
+        F32/F16/BF16: the element in row r, column c of the segment is
+        element t = scale_e0 + r * scale_pitch + c of the tensor and is
+        multiplied by the f32 scale of its bm x bn tile,
+        scale_ptr[block_scale_index(t, M, K, bm, bn)], one
+        block_load_kernel launch for all of them."""
+        plain, mx, block = _split_mx(segments)
         if plain:
             self._n.arena_convert_ptr(self.handle, plain)
         if mx:
             self._n.arena_mx_convert_ptr(self.handle, mx)
+        if block:
+            self._n.arena_block_convert_ptr(self.handle, block)
 
     def store_ptr(self, segments: list[tuple]) -> None:
         """Typed store, the scatter direction of convert_ptr: each segment
@@ -187,12 +197,19 @@ class Arena:
         An 11-tuple appends (scale_ptr, scale_e0, scale_pitch, 32) and
         quantises F32/F16/BF16 -> F8_E4M3 or F4 under the E8M0 block
         scales of mx_scales, as in convert_ptr: one mx_store_kernel launch
-        for all of them."""
-        plain, mx = _split_mx(segments)
+        for all of them.
+
+        A 14-tuple appends (scale_ptr, scale_e0, scale_pitch, M, K, bm,
+        bn) and quantises F32/F16/BF16 -> F8_E4M3 under the f32 tile
+        scales of block_absmax_scales, as in convert_ptr: one
+        block_store_kernel launch for all of them."""
+        plain, mx, block = _split_mx(segments)
         if plain:
             self._n.arena_store_ptr(self.handle, plain)
         if mx:
             self._n.arena_mx_store_ptr(self.handle, mx)
+        if block:
+            self._n.arena_block_store_ptr(self.handle, block)
 
     def lz4_compress(self, off: int, n: int) -> bytes:
         """Compress arena bytes [off, off+n) into a CVLZ container (HIP
@@ -237,10 +254,11 @@ class Arena:
 
 
 def _split_mx(segments):
-    """(7- and 10-tuples, 11-tuples): the MX segments have kernels of
-    their own."""
-    plain = [s for s in segments if len(s) != 11]
-    return plain, [s for s in segments if len(s) == 11]
+    """(7- and 10-tuples, 11-tuples, 14-tuples): the MX and the
+    block-scaled segments have kernels of their own."""
+    plain = [s for s in segments if len(s) not in (11, 14)]
+    return plain, [s for s in segments if len(s) == 11], \
+        [s for s in segments if len(s) == 14]
 
 
 def hip_pool_stats() -> dict:
@@ -355,6 +373,57 @@ def mx_convert_host(buf, src_dtype: int, dst_dtype: int, n: int, scales,
     element i uses the E8M0 byte scales[(scale_e0 + i) // 32]."""
     return load().mx_convert_host(buf, src_dtype, dst_dtype, n, scales,
                                   scale_e0)
+
+
+# the block-scaled pairs: F32/F16/BF16 <-> F8_E4M3 with one f32 scale per
+# bm x bn tile of the last two dimensions
+BLOCK_DEFAULT = (128, 128)
+
+
+def block_quantize_supported(src: str) -> bool:
+    """`src` can be stored as block-scaled F8_E4M3."""
+    return src in QUANTIZE_SOURCES
+
+
+def block_dequantize_supported(dst: str) -> bool:
+    """Block-scaled F8_E4M3 can be loaded as `dst`."""
+    return dst in DEQUANTIZE_TARGETS
+
+
+def block_scale_shape(shape, block) -> tuple:
+    """Shape of the f32 scales of a tensor (..., M, K) under bm x bn tiles:
+    shape[:-2] + (ceil(M / bm), ceil(K / bn))."""
+    bm, bn = block
+    return tuple(shape[:-2]) + (-(-shape[-2] // bm), -(-shape[-1] // bn))
+
+
+def block_absmax_scales(device: int, segments: list[tuple]) -> None:
+    """Fill the f32 tile scales for a block-quantising store.  Each
+    segment is (src_ptr, rows, run, src_pitch, src_dtype, out_ptr,
+    scale_e0, scale_pitch, M, K, bm, bn, n_slots): `rows` runs of `run`
+    F32/F16/BF16 elements, `src_pitch` bytes apart at `src_ptr`; the
+    element in row r, column c is element t = scale_e0 + r * scale_pitch +
+    c of a tensor (..., M, K) and belongs to the tile
+    ((t // K // M) * ceil(M/bm) + (t // K % M) // bm) * ceil(K/bn)
+    + (t % K) // bn, whose scale is out_ptr[tile].  out_ptr[0:n_slots]
+    becomes max(amax, 2**-40) / 448 with amax the largest finite |x| of the
+    tile; edge tiles reduce over the elements that exist.  device >= 0: one
+    block_absmax_kernel launch for the whole list on that GPU, synchronised
+    on return; device == -1: the same routine in C++ over host memory.  Bad
+    arguments raise ValueError before anything runs."""
+    load().block_absmax_scales(device, segments)
+
+
+def block_convert_host(buf, src_dtype: int, dst_dtype: int, n: int, scales,
+                       scale_e0: int, m: int, k: int, bm: int, bn: int,
+                       scale_g0: int = 0) -> bytes:
+    """Quantise (F32/F16/BF16 -> F8_E4M3) or dequantise (the reverse) `n`
+    packed elements on the host with the kernels' own routines; element i
+    is element scale_e0 + i of a tensor (..., m, k) under bm x bn tile
+    scales, `scales` holding the tensor's f32 scales from index scale_g0
+    on."""
+    return load().block_convert_host(buf, src_dtype, dst_dtype, n, scales,
+                                     scale_e0, m, k, bm, bn, scale_g0)
 
 
 def convert_host(buf, src_dtype: int, dst_dtype: int, n: int, scales=None,

@@ -33,6 +33,15 @@ for bit: s = max(E - emax, 0) from the biased f32 exponent E of the block's
 largest finite |x|, q = x * 2**(127-s) rounded once, ties to even,
 saturating, y = value(q) * 2**(s-127) rounded once.
 
+Block-scaled FP8 checkpoints (a `weight` plus a `weight_scale_inv`, the
+`quant_method: fp8` / `weight_block_size: [128, 128]` layout):
+`save_file(quantize="block", quantize_block=(128, 128))` stores the
+selected tensors as `F8_E4M3` next to an F32 `name + "_scale_inv"` of shape
+shape[:-2] + (ceil(M/bm), ceil(K/bn)), one scale per bm x bn tile of the
+last two dimensions; `load(dequantize=True)` multiplies every element by
+its tile's scale in `block_load_kernel` (csrc/block_cast.hip).  The
+numerics are those of the "row" mode, per tile.
+
 The header parser and writer are written here by hand: the `safetensors`
 package is not a dependency.
 """
@@ -43,12 +52,30 @@ import struct
 from dataclasses import dataclass
 
 from curvine_amd import errors as err
-from curvine_amd.native import (CONVERT_SOURCES, DTYPE_BITS, DTYPE_ITEMSIZE,
-                                DTYPES, MX_BLOCK, convert_supported,
-                                dequantize_supported, mx_dequantize_supported,
+from curvine_amd.native import (BLOCK_DEFAULT, CONVERT_SOURCES, DTYPE_BITS,
+                                DTYPE_ITEMSIZE, DTYPES, MX_BLOCK,
+                                block_dequantize_supported,
+                                block_quantize_supported, block_scale_shape,
+                                convert_supported, dequantize_supported,
+                                mx_dequantize_supported,
                                 mx_quantize_supported, quantize_supported)
 
 MAX_HEADER = 100 << 20
+BLOCK_META_KEY = "weight_block_size"      # __metadata__: "bm,bn"
+
+
+def _check_block(block, what: str) -> tuple:
+    """`block` as two positive ints, else InvalidArgument."""
+    try:
+        ok = len(block) == 2 and all(
+            isinstance(v, int) and not isinstance(v, bool) and v > 0
+            for v in block)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise err.InvalidArgument(
+            f"safetensors: {what} must be two positive ints, not {block!r}")
+    return tuple(block)
 
 
 @dataclass(frozen=True)
@@ -274,11 +301,42 @@ class CurvineSafetensors:
         return (out_shape, outer, part * inner, shape[dim] * inner,
                 rank * part * inner)
 
-    def _scale_info(self, info: TensorInfo):
+    def _block_of(self, scale_block) -> tuple:
+        """(bm, bn) of this file's block-scaled tensors: the keyword, else
+        `__metadata__["weight_block_size"]` ("bm,bn"; a value that does
+        not read as two positive ints counts as absent), else (128, 128)."""
+        if scale_block is not None:
+            return _check_block(scale_block, "scale_block")
+        try:
+            bm, bn = (int(v) for v in
+                      self._meta.get(BLOCK_META_KEY, "").strip("[]() ")
+                      .split(","))
+            return _check_block((bm, bn), BLOCK_META_KEY)
+        except (ValueError, err.InvalidArgument):
+            return BLOCK_DEFAULT
+
+    def _scale_info(self, info: TensorInfo, block=BLOCK_DEFAULT):
         """The F32 `name + "_scale"` entry that makes a stored F8_E4M3
         tensor a scaled one (one scale, or one per index of dim 0), or
         the F8_E8M0 one of shape shape[:-1] + (K // 32,) that makes a
-        stored F8_E4M3 or F4 tensor an MX one, else None."""
+        stored F8_E4M3 or F4 tensor an MX one; failing both, the F32
+        `name + "_scale_inv"` of shape shape[:-2] + (ceil(M/bm),
+        ceil(K/bn)) that makes a stored F8_E4M3 tensor (..., M, K) a
+        block-scaled one; else None."""
+        s = self._plain_scale_info(info)
+        if s is not None or info.dtype != "F8_E4M3" or len(info.shape) < 2:
+            return s
+        s = self._infos.get(info.name + "_scale_inv")
+        if s is not None and s.dtype == "F32" and \
+                s.shape == block_scale_shape(info.shape, block):
+            return s
+        return None
+
+    @staticmethod
+    def _is_block(info: TensorInfo, sinfo: TensorInfo) -> bool:
+        return sinfo.name == info.name + "_scale_inv"
+
+    def _plain_scale_info(self, info: TensorInfo):
         if info.dtype not in _MX_STORED:
             return None
         s = self._infos.get(info.name + "_scale")
@@ -296,13 +354,20 @@ class CurvineSafetensors:
         return None
 
     def _scale_fields(self, info: TensorInfo, sinfo: TensorInfo, shard,
-                      out_shape, scale_ptr: int):
+                      out_shape, scale_ptr: int, block=BLOCK_DEFAULT):
         """(scale_ptr, scale_every, scale_e0) of a request for `info` or
         its shard, the tensor's scales being at scale_ptr.  For an MX
         tensor (scale_ptr, scale_e0, scale_pitch, 32): the request's first
         element and the distance of its runs, both in elements of the
         tensor and multiples of 32, so a run's block scales start at byte
-        scale_e0 // 32 and lie scale_pitch // 32 bytes apart."""
+        scale_e0 // 32 and lie scale_pitch // 32 bytes apart.  For a
+        block-scaled tensor (scale_ptr, scale_e0, scale_pitch, M, K, bm,
+        bn): the same two tensor indices, any shard, the whole scale
+        tensor."""
+        if self._is_block(info, sinfo):
+            _, rows, run, pitch_el, first = self._slice(info, shard)
+            return (scale_ptr, first, pitch_el) + info.shape[-2:] + \
+                tuple(block)
         if sinfo.dtype == "F8_E8M0":
             _, rows, run, pitch_el, first = self._slice(info, shard)
             if run % MX_BLOCK:
@@ -357,7 +422,8 @@ class CurvineSafetensors:
 
     # ---- loading ----
     def load(self, device="cuda:0", dtype=None, names=None,
-             shard_plan=None, dequantize: bool = False) -> dict:
+             shard_plan=None, dequantize: bool = False,
+             scale_block=None) -> dict:
         """All (or `names`) tensors in one batched pass: every destination
         is allocated, every tensor resolved, then ONE convert call per
         arena covers the whole file.
@@ -373,16 +439,33 @@ class CurvineSafetensors:
         torch.float8_e8m0fnu and F4 as torch.float4_e2m1fn_x2 with the
         last dimension halved.  That takes two batched passes: the scales go to F32 tensors
         on `device` first, then everything else with the weights pointing
-        at them.  An F8_E4M3 tensor without such a scale loads as ever."""
+        at them.  An F8_E4M3 tensor without such a scale loads as ever.
+
+        Block-scaled tensors (`quant_method: fp8` with `weight_block_size`
+        in Hugging Face terms): a stored F8_E4M3 tensor N of shape
+        (..., M, K) without such a `_scale` whose file holds an F32
+        `N + "_scale_inv"` of shape shape[:-2] + (ceil(M/bm), ceil(K/bn))
+        comes back as `(q.float() * s_tile).to(dst)`, one scale per
+        bm x bn tile of each matrix, applied in block_load_kernel
+        (csrc/block_cast.hip); the `_scale_inv` entry is hidden like a
+        `_scale`.  (bm, bn) is `scale_block`, or when None the file's
+        `__metadata__["weight_block_size"]` ("bm,bn"), or (128, 128);
+        anything but two positive ints is InvalidArgument.  A `_scale_inv`
+        of another shape leaves the tensor unscaled.  Shards along any
+        dimension and of any part size work, parts that cut tiles
+        included: every element looks its scale up by its own
+        coordinates, so the result is the slice of the whole dequantised
+        tensor."""
         import torch
         dev = torch.device(device)
         tmap = _torch_dtypes()
         shard_plan = shard_plan or {}
         wanted = self.keys() if names is None else list(names)
         scaled = {}
+        block = self._block_of(scale_block)
         if dequantize:
             for name in wanted:
-                sinfo = self._scale_info(self.info(name))
+                sinfo = self._scale_info(self.info(name), block)
                 if sinfo is not None:
                     scaled[name] = sinfo
             if names is None:
@@ -414,7 +497,7 @@ class CurvineSafetensors:
         self._execute(
             [req if name not in scaled else req + self._scale_fields(
                 self.info(name), scaled[name], shard, shape,
-                scales[scaled[name].name].data_ptr())
+                scales[scaled[name].name].data_ptr(), block)
              for name, shard, shape, req in requests], dev)
         return out
 
@@ -454,16 +537,19 @@ class CurvineSafetensors:
         return out
 
     def get_tensor(self, name: str, device="cuda:0", dtype=None, shard=None,
-                   dequantize: bool = False):
+                   dequantize: bool = False, scale_block=None):
         plan = None if shard is None else {name: shard}
-        return self.load(device, dtype, [name], plan, dequantize)[name]
+        return self.load(device, dtype, [name], plan, dequantize,
+                         scale_block)[name]
 
     def load_into(self, name: str, tensor, shard=None,
-                  dequantize: bool = False) -> None:
+                  dequantize: bool = False, scale_block=None) -> None:
         """Fill an existing tensor (a module parameter): destination dtype
-        and device come from `tensor`.  `dequantize` as in load()."""
+        and device come from `tensor`.  `dequantize` and `scale_block` as
+        in load()."""
         info = self.info(name)
-        sinfo = self._scale_info(info) if dequantize else None
+        block = self._block_of(scale_block)
+        sinfo = self._scale_info(info, block) if dequantize else None
         stored = info.dtype
         if sinfo is None and stored in _MX_BYTES:
             info = self._byte_view(info, shard)
@@ -482,7 +568,9 @@ class CurvineSafetensors:
         t2s = {v: k for k, v in _torch_dtypes().items()}
         dst_name = t2s.get(tensor.dtype)
         if dst_name is None or not (
-                dequantize_supported(dst_name) if sinfo is not None
+                (block_dequantize_supported(dst_name)
+                 if self._is_block(info, sinfo)
+                 else dequantize_supported(dst_name)) if sinfo is not None
                 else convert_supported(stored, dst_name)):
             raise err.Unsupported(
                 f"safetensors: tensor {name!r}: cannot load {stored} "
@@ -493,7 +581,8 @@ class CurvineSafetensors:
             if sinfo is not None:
                 scales = self._load_scales([sinfo], tensor.device)
                 req += self._scale_fields(info, sinfo, shard, shape,
-                                          scales[sinfo.name].data_ptr())
+                                          scales[sinfo.name].data_ptr(),
+                                          block)
             self._execute([req], tensor.device)
 
     def close(self) -> None:
@@ -507,10 +596,11 @@ class CurvineSafetensors:
 
 
 def load_file(sync_fs, path: str, device="cuda:0", dtype=None,
-              dequantize: bool = False) -> dict:
+              dequantize: bool = False, scale_block=None) -> dict:
     """One-shot: cached safetensors path -> {name: tensor}."""
     with CurvineSafetensors(sync_fs, path) as f:
-        return f.load(device=device, dtype=dtype, dequantize=dequantize)
+        return f.load(device=device, dtype=dtype, dequantize=dequantize,
+                      scale_block=scale_block)
 
 
 # ---------------------------------------------------------------- saving
@@ -553,13 +643,20 @@ def _host_reader(t, rows: int, run: int, pitch: int):
     return read_host
 
 
-QUANTIZE_MODES = ("tensor", "row", "mxfp8", "mxfp4")
+QUANTIZE_MODES = ("tensor", "row", "mxfp8", "mxfp4", "block")
 MX_MODES = {"mxfp8": "F8_E4M3", "mxfp4": "F4"}     # mode -> element dtype
 
 
 def _quantize_default(name, t) -> bool:
     return t.is_floating_point() and t.element_size() in (2, 4) and \
         t.ndim >= 2 and t.numel() > 0
+
+
+def _numel(shape) -> int:
+    n = 1
+    for d in shape:
+        n *= d
+    return n
 
 
 def _scales_host(scale):
@@ -575,7 +672,7 @@ def _scales_host(scale):
 
 
 def _save_plan(tensors: dict, metadata, dtype, quantize=None,
-               quantize_filter=None):
+               quantize_filter=None, quantize_block=None):
     """(header bytes, [TypedSource], tensors kept alive).  Raises before
     anything touches the cluster."""
     import torch
@@ -594,6 +691,28 @@ def _save_plan(tensors: dict, metadata, dtype, quantize=None,
             f"safetensors: quantize must be one of {QUANTIZE_MODES}, not "
             f"{quantize!r}")
     mx = MX_MODES.get(quantize)
+    block = None
+    if quantize == "block":
+        # the tile geometry is part of the format a file is written in:
+        # it is named by the caller, never assumed
+        if quantize_block is None:
+            raise err.InvalidArgument(
+                'safetensors: quantize="block" needs quantize_block=(bm, '
+                'bn), e.g. (128, 128)')
+        block = _check_block(quantize_block, "quantize_block")
+        want = f"{block[0]},{block[1]}"
+        if metadata is not None and \
+                metadata.get(BLOCK_META_KEY, want) != want:
+            raise err.InvalidArgument(
+                f"safetensors: metadata {BLOCK_META_KEY!r} is "
+                f"{metadata[BLOCK_META_KEY]!r} but quantize_block gives "
+                f"{want!r}")
+        metadata = dict(metadata or {})
+        metadata[BLOCK_META_KEY] = want
+    elif quantize_block is not None:
+        raise err.InvalidArgument(
+            'safetensors: quantize_block needs quantize="block"')
+    suffix = "_scale_inv" if block else "_scale"
     forced = quantize_filter is not None
     if quantize_filter is None:
         quantize_filter = _quantize_default
@@ -633,10 +752,19 @@ def _save_plan(tensors: dict, metadata, dtype, quantize=None,
                 raise err.InvalidArgument(
                     f"safetensors: tensor {name!r}: last dimension of shape "
                     f"{shape} is not a multiple of {MX_BLOCK}")
-            if name + "_scale" in tensors:
+            if block and t.ndim < 2:
                 raise err.InvalidArgument(
-                    f"safetensors: {name + '_scale'!r} is both a given "
+                    f"safetensors: tensor {name!r}: shape {shape} has no "
+                    f"two dimensions to tile")
+            if name + suffix in tensors:
+                raise err.InvalidArgument(
+                    f"safetensors: {name + suffix!r} is both a given "
                     f"tensor and the scale of {name!r}")
+            if block and name + "_scale" in tensors:
+                raise err.InvalidArgument(
+                    f"safetensors: the given tensor {name + '_scale'!r} "
+                    f"would win over {name + suffix!r} when {name!r} is "
+                    f"loaded")
             dst = mx or "F8_E4M3"
         elif dtype is not None and src in _FLOATING:
             dst = t2s.get(dtype)
@@ -655,11 +783,12 @@ def _save_plan(tensors: dict, metadata, dtype, quantize=None,
         if dst != src and dst in _MX_STORED:
             n_groups[device] = n_groups.get(device, 0) + (
                 t.numel() // MX_BLOCK if mx else
+                _numel(block_scale_shape(shape, block)) if block else
                 t.shape[0] if quantize == "row" else 1)
 
     # one buffer per device holds every scale of the checkpoint (F32, or
-    # E8M0 bytes for the MX modes): each `name + "_scale"` is a view of it,
-    # saved like any given tensor
+    # E8M0 bytes for the MX modes): each `name + "_scale"` (block mode:
+    # `name + "_scale_inv"`) is a view of it, saved like any given tensor
     scale_of, used = {}, {}
     sdt = "F8_E8M0" if mx else "F32"
     bufs = {d: torch.empty(n, dtype=torch.uint8 if mx else torch.float32,
@@ -671,6 +800,9 @@ def _save_plan(tensors: dict, metadata, dtype, quantize=None,
         if mx:
             n, view = t.numel() // MX_BLOCK, \
                 shape[:-1] + (shape[-1] // MX_BLOCK,)
+        elif block:
+            view = block_scale_shape(shape, block)
+            n = _numel(view)
         else:
             n = t.shape[0] if quantize == "row" else 1
             view = (n, 1) if quantize == "row" else (1,)
@@ -678,7 +810,7 @@ def _save_plan(tensors: dict, metadata, dtype, quantize=None,
         used[device] = o + n
         scale = bufs[device][o:o + n].view(view)
         scale_of[name] = scale
-        entries.append((name + "_scale", scale, sdt, sdt, device, view))
+        entries.append((name + suffix, scale, sdt, sdt, device, view))
     entries.sort(key=lambda e: (-DTYPE_BITS[e[3]], e[0]))
 
     hdr, keep, sources, pos = {}, list(bufs.values()), [], 0
@@ -713,6 +845,16 @@ def _save_plan(tensors: dict, metadata, dtype, quantize=None,
                 absmax.setdefault(device, []).append(
                     (t.data_ptr(), rows, run, source.pitch, DTYPES[src],
                      DTYPES[dst], scale.data_ptr()))
+            elif scale is not None and block:
+                # the dense side is the tensor: tiles follow its last two
+                # dimensions whatever the layout collapsed to
+                source.block = tuple(shape[-2:]) + block
+                source.scale_ptr = scale.data_ptr()
+                source.scales_host = _scales_host(scale)
+                absmax.setdefault(device, []).append(
+                    (t.data_ptr(), rows, run, source.pitch, DTYPES[src],
+                     scale.data_ptr(), 0, run) + source.block +
+                    (scale.numel(),))
             elif scale is not None:
                 # groups follow the tensor's dim 0 whatever the layout
                 # collapsed to
@@ -733,12 +875,14 @@ def _save_plan(tensors: dict, metadata, dtype, quantize=None,
             # still has in flight for these tensors must be done
             torch.cuda.current_stream(device).synchronize()
         segs = absmax.get(device, [])
-        if not segs and not mx:          # only empty weights: floor scales
+        if not segs and not mx and not block:   # only empty weights: floor
             segs = [(0, 0, 0, 0, DTYPES["F32"], buf.data_ptr(), 0, 0,
                      buf.numel())]
         try:
             if mx:
                 native.mx_scales(device, segs)
+            elif block:
+                native.block_absmax_scales(device, segs)
             else:
                 native.absmax_scales(device, segs)
         except ValueError as e:
@@ -754,7 +898,7 @@ def _save_plan(tensors: dict, metadata, dtype, quantize=None,
 def save_file(sync_fs, tensors: dict, path: str, metadata=None, dtype=None,
               storage_tier: str = "", block_size: int = 0,
               overwrite: bool = False, replicas: int = 0, quantize=None,
-              quantize_filter=None):
+              quantize_filter=None, quantize_block=None):
     """Save {name: tensor} as a safetensors file in the cache; returns its
     FileStatus.  Blocks that land in the HBM arena of the tensors' own GPU
     (or in a host arena, for cpu tensors) are written by the typed store:
@@ -806,9 +950,29 @@ def save_file(sync_fs, tensors: dict, path: str, metadata=None, dtype=None,
     selected tensor that is not F32/F16/BF16 (Unsupported).  The scales
     are computed on the tensors' device, one absmax_segments_kernel launch
     per device for the whole checkpoint, and views are quantised in
-    place."""
+    place.
+
+    `quantize="block"` stores them as block-scaled `F8_E4M3` (the layout
+    of `quant_method: fp8` checkpoints with `weight_block_size`): each
+    next to an F32 `name + "_scale_inv"` of shape shape[:-2] +
+    (ceil(M/bm), ceil(K/bn)), one scale per bm x bn tile of the last two
+    dimensions (leading dimensions are batches of matrices), w = q *
+    scale_inv.  (bm, bn) is `quantize_block`, which the mode requires:
+    the geometry of a written file is named, never assumed, so
+    `quantize="block"` alone is InvalidArgument; (128, 128) is what the
+    checkpoints that ship this layout use and what load() assumes.  The
+    scale and the cast are those of "row" applied per tile, edge tiles
+    reducing over the elements that exist.  `weight_block_size: "bm,bn"`
+    is added to `__metadata__` (created when none was given).  The default
+    selection is that of "row".  Also refused before anything touches the
+    cluster (InvalidArgument): a `quantize_block` that is not two positive
+    ints or comes with another mode, a caller's own `weight_block_size`
+    that differs, a `name + "_scale_inv"` that is also a given tensor (or
+    a `name + "_scale"`, which would win over it on load), a
+    selected tensor with fewer than two dimensions.  The scales come from
+    one block_absmax_kernel launch per device (csrc/block_cast.hip)."""
     header, sources, keep = _save_plan(tensors, metadata, dtype, quantize,
-                                       quantize_filter)
+                                       quantize_filter, quantize_block)
     devices = sorted({s.device for s in sources if s.device >= 0})
     if devices:
         import torch

@@ -74,7 +74,9 @@ class BlockWriter:
         cannot take a pointer raise Unsupported: the caller then writes
         bytes.  A piece may append (scale_ptr, scale_every, scale_e0): the
         quantising store of Arena.store_ptr, or (scale_ptr, scale_e0,
-        scale_pitch, 32), its MX store.  Returns the bytes written."""
+        scale_pitch, 32), its MX store, or (scale_ptr, scale_e0,
+        scale_pitch, M, K, bm, bn), its block-scaled store.  Returns the
+        bytes written."""
         from curvine_amd.native import DTYPE_BITS, DTYPES
         bits = {DTYPES[k]: v for k, v in DTYPE_BITS.items()}
         total, top = 0, self.pos
