@@ -153,6 +153,7 @@ static uint32_t crc32c_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
 #include "tensor_cast.hip"
 #include "mx_cast.hip"
 #include "block_cast.hip"
+#include "token_gather.hip"
 
 // ---------------------------------------------------------------------------
 // GPU availability
@@ -1252,6 +1253,134 @@ static py::bytes convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
   in.b = (uint64_t)(uintptr_t)out.data();
   CastSeg g = cast_validate((uint64_t)bi.size * bi.itemsize, in, true);
   if (g.rows * g.run) convert_segment_host((const uint8_t*)bi.ptr, g);
+  return py::bytes((const char*)out.data(), out_b);
+}
+
+// ---- token windows (token_gather.hip) ----
+//
+// Pieces: (src_off, row, j0, n): n source tokens at arena byte src_off are
+// tokens j0 .. j0+n-1 of window `row` of `batch` windows of seq_len + 1
+// tokens; token j lands at x[row*seq_len + j] (j < seq_len) and at
+// y[row*seq_len + j - 1] (j >= 1), widened src_dtype -> dst_dtype.  Returns
+// the tokens read that lie outside [0, vocab_size) (0 when vocab_size is 0).
+// Every argument error is raised here, on the host, before anything runs.
+typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t> TokenPieceTuple;
+
+static uint64_t arena_token_windows(int h, std::vector<TokenPieceTuple> pieces_in,
+                                    uintptr_t x_ptr, uintptr_t y_ptr,
+                                    uint64_t batch, uint64_t seq_len,
+                                    uint64_t sdt, uint64_t ddt,
+                                    uint64_t vocab) {
+  Arena* a = get_arena(h);
+  if (sdt >= DT_COUNT || ddt >= DT_COUNT)
+    throw std::invalid_argument("token windows: unknown dtype code");
+  if (!token_pair_supported((uint32_t)sdt, (uint32_t)ddt))
+    throw std::invalid_argument("token windows: unsupported dtype pair");
+  if (batch == 0 || seq_len == 0)
+    throw std::invalid_argument("token windows: batch and seq_len must be positive");
+  uint64_t ss = cast_itemsize((uint32_t)sdt), ds = cast_itemsize((uint32_t)ddt);
+  uint64_t win, n_el, dst_b, x_end, y_end;
+  if (__builtin_add_overflow(seq_len, (uint64_t)1, &win) ||
+      __builtin_mul_overflow(batch, seq_len, &n_el) ||
+      __builtin_mul_overflow(n_el, ds, &dst_b) ||
+      __builtin_add_overflow((uint64_t)x_ptr, dst_b, &x_end) ||
+      __builtin_add_overflow((uint64_t)y_ptr, dst_b, &y_end))
+    throw std::invalid_argument("token windows: destination size overflows");
+  if (x_ptr == 0 || x_ptr % ds)
+    throw std::invalid_argument("token windows: x_ptr null or misaligned");
+  if (y_ptr == 0 || y_ptr % ds)
+    throw std::invalid_argument("token windows: y_ptr null or misaligned");
+  std::vector<TokenPiece> pieces;
+  pieces.reserve(pieces_in.size());
+  for (auto& t : pieces_in) {
+    TokenPiece g{std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t)};
+    uint64_t last, src_b, end;
+    if (g.n == 0)
+      throw std::invalid_argument("token windows: piece without tokens");
+    if (g.row >= batch)
+      throw std::invalid_argument("token windows: piece row outside the batch");
+    if (__builtin_add_overflow(g.j0, g.n, &last) ||
+        __builtin_mul_overflow(g.n, ss, &src_b) ||
+        __builtin_add_overflow(g.src_off, src_b, &end))
+      throw std::invalid_argument("token windows: piece range overflows");
+    if (last > win)
+      throw std::invalid_argument("token windows: piece runs past its window");
+    if (end > a->cap)
+      throw std::invalid_argument("token windows: arena range out of bounds");
+    pieces.push_back(g);
+  }
+  py::gil_scoped_release rel;
+  uint8_t* x = (uint8_t*)x_ptr;
+  uint8_t* y = (uint8_t*)y_ptr;
+  if (!a->is_dev()) {
+    // a host arena scatters with the CPU: device memory is the wrong side
+    for (uintptr_t p : {x_ptr, y_ptr}) {
+      hipPointerAttribute_t at;
+      if (hipPointerGetAttributes(&at, (const void*)p) != hipSuccess) {
+        (void)hipGetLastError();   // plain host memory, or no runtime
+        continue;
+      }
+      if (at.type == hipMemoryTypeDevice)
+        throw std::invalid_argument(
+            "token windows: device destination on a host arena");
+    }
+    uint64_t bad = 0;
+    for (auto& g : pieces)
+      bad += token_windows_host((const uint8_t*)a->base, g, x, y, seq_len,
+                                (uint32_t)sdt, (uint32_t)ddt, vocab);
+    return bad;
+  }
+  Tiles tiles = build_tiles(
+      pieces.size(), [&](size_t i) { return pieces[i].n; },
+      [](size_t) { return (uint64_t)TOKEN_TILE; }, "token windows");
+  std::lock_guard<std::mutex> g(a->mu);
+  HIP_CHECK(hipSetDevice(a->device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  check_device_range(a->device, x_ptr, x_end, "token windows", "x_ptr",
+                     "destination", known);
+  check_device_range(a->device, y_ptr, y_end, "token windows", "y_ptr",
+                     "destination", known);
+  if (tiles.empty()) return 0;   // nothing to gather: no grid-0 launch
+  Scratch sc(a, Scratch::room<unsigned long long>(1) +
+                    tiles.room<TokenPiece>(pieces.size()));
+  unsigned long long* d_count = sc.take<unsigned long long>(1);
+  if (vocab) HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(*d_count), a->kstream));
+  DevTiles<TokenPiece> d = upload_tiles(a, sc, pieces, tiles);
+  launch(token_windows_kernel, d.grid(), WG, a->kstream,
+         (const uint8_t*)a->base, d.items, d.tile_item, d.tile_off, d.n_tiles,
+         x, y, seq_len, (uint32_t)sdt, (uint32_t)ddt, vocab, d_count);
+  unsigned long long bad = 0;
+  if (vocab)
+    HIP_CHECK(hipMemcpyAsync(&bad, d_count, sizeof(bad), hipMemcpyDeviceToHost,
+                             a->kstream));
+  HIP_CHECK(hipStreamSynchronize(a->kstream));
+  return bad;
+}
+
+// host widening of `n` packed tokens (the slow path of the token reader:
+// file-tier spans and the token that straddles a block boundary go through
+// the kernel's own scalar routine)
+static py::bytes token_convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
+                                    uint64_t n) {
+  py::buffer_info bi = src.request();
+  if (sdt >= DT_COUNT || ddt >= DT_COUNT)
+    throw std::invalid_argument("token convert: unknown dtype code");
+  if (!token_pair_supported((uint32_t)sdt, (uint32_t)ddt))
+    throw std::invalid_argument("token convert: unsupported dtype pair");
+  uint32_t ss = cast_itemsize((uint32_t)sdt), ds = cast_itemsize((uint32_t)ddt);
+  uint64_t src_b, out_b;
+  if (__builtin_mul_overflow(n, (uint64_t)ss, &src_b) ||
+      __builtin_mul_overflow(n, (uint64_t)ds, &out_b) || out_b > (1ull << 40))
+    throw std::invalid_argument("token convert: size overflows");
+  if (src_b > (uint64_t)bi.size * bi.itemsize)
+    throw std::invalid_argument("token convert: source shorter than n tokens");
+  // 8-byte words: aligned for both destination itemsizes
+  std::vector<uint64_t> out(out_b / 8 + 1);
+  const uint8_t* s = (const uint8_t*)bi.ptr;
+  uint8_t* d = (uint8_t*)out.data();
+  for (uint64_t i = 0; i < n; ++i)
+    token_store(d + i * ds, token_widen(token_load(s + i * ss, ss), (uint32_t)sdt),
+                ds);
   return py::bytes((const char*)out.data(), out_b);
 }
 
@@ -2708,6 +2837,8 @@ PYBIND11_MODULE(_native, m) {
   m.def("convert_host", &convert_host, py::arg("src"), py::arg("src_dtype"),
         py::arg("dst_dtype"), py::arg("n"), py::arg("scales") = py::none(),
         py::arg("scale_every") = 0, py::arg("scale_e0") = 0);
+  m.def("arena_token_windows", &arena_token_windows);
+  m.def("token_convert_host", &token_convert_host);
   m.def("absmax_scales", &absmax_scales);
   m.def("arena_mx_store_ptr", &arena_mx_store_ptr);
   m.def("arena_mx_convert_ptr", &arena_mx_convert_ptr);
@@ -2793,5 +2924,6 @@ PYBIND11_MODULE(_native, m) {
   m.def("crc32c_combine", &crc32c_combine);
   m.attr("CRC_SUB") = CRC_SUB;
   m.attr("CAST_TILE") = CAST_TILE;
+  m.attr("TOKEN_TILE") = TOKEN_TILE;
   m.attr("__hip_arch__") = "gfx950";
 }

@@ -474,6 +474,101 @@ class SyncLocalReader:
                                       native.DTYPES[ddt], n, **kw)
             self._land(out, dptr, dst_on_device)
 
+    # ---------------- token windows ----------------
+    def resolve_token_windows(self, windows, src_dtype: str, seq_len: int,
+                              dst_on_device: bool):
+        """Resolution half of a token-window batch, modelled on
+        resolve_convert.  windows = [(file_off, row)]: window `row` is
+        seq_len + 1 tokens of `src_dtype` (a name from
+        native.TOKEN_SOURCES) starting at byte file_off.  Returns (groups,
+        slow): groups = [(arena, pieces)] with pieces (src_off, row, j0, n)
+        ready for Arena.token_windows, for spans inside one arena block on
+        the destinations' side; slow = [(file_off, row, j0, n)] for the
+        pread + host path: file tier, cross-side arenas, holes (which read
+        as zeros) and the single token that straddles two blocks when
+        tokens sit at odd offsets.  Pieces split on whole tokens.  A window
+        that runs past the end of the file is OutOfRange."""
+        import bisect
+
+        from curvine_amd.native import DTYPE_ITEMSIZE
+        ss = DTYPE_ITEMSIZE[src_dtype]
+        n_tok = seq_len + 1
+        groups: dict[int, tuple[object, list]] = {}
+        slow: list[tuple[int, int, int, int]] = []
+        blocks = self.fb.blocks
+        for off, row in windows:
+            if off < 0 or off + n_tok * ss > self.length:
+                raise err.OutOfRange(
+                    f"token window at {off}: {n_tok} tokens run past the "
+                    f"file's {self.length} bytes")
+            e = 0
+            while e < n_tok:
+                p = off + e * ss
+                hole = _hole_span(self._offs, blocks, self.length, p)
+                if hole > 0:          # pread synthesizes zeros
+                    k = min(n_tok - e, -(-hole // ss))
+                    slow.append((p, row, e, k))
+                    e += k
+                    continue
+                idx = bisect.bisect_right(self._offs, p) - 1
+                lb = blocks[idx]
+                k = min(n_tok - e, (lb.offset + lb.block.length - p) // ss)
+                if k == 0:            # token straddles two blocks
+                    slow.append((p, row, e, 1))
+                    e += 1
+                    continue
+                r = self._readers[idx]
+                arena = getattr(r.layout, "arena", None)
+                same_side = r.meta.get("kind") == "arena" and \
+                    arena is not None and \
+                    ((arena.device >= 0) == bool(dst_on_device))
+                if same_side:
+                    _, pieces = groups.setdefault(arena.handle, (arena, []))
+                    pieces.append((r.meta["offset"] + p - lb.offset, row, e, k))
+                else:
+                    slow.append((p, row, e, k))
+                e += k
+        return list(groups.values()), slow
+
+    def exec_token_windows(self, groups, slow, x_ptr: int, y_ptr: int,
+                           batch: int, seq_len: int, src_dtype: str,
+                           dst_dtype: str, vocab_size: int,
+                           dst_on_device: bool) -> int:
+        """Run a resolve_token_windows plan into x and y, two dense
+        [batch, seq_len] arrays of dst_dtype: one Arena.token_windows per
+        arena, then the slow list through pread -> host widen (the kernel's
+        own routine) -> H2D copy or memcpy, into the x span and the y span
+        of each entry.  Returns the tokens outside [0, vocab_size), the
+        slow ones counted here by the same rule (0 when vocab_size is 0)."""
+        from curvine_amd import native
+        sc, dc = native.DTYPES[src_dtype], native.DTYPES[dst_dtype]
+        ss = native.DTYPE_ITEMSIZE[src_dtype]
+        ds = native.DTYPE_ITEMSIZE[dst_dtype]
+        fmt = {"U16": "H", "U32": "I", "I32": "i"}[src_dtype]
+        bad = 0
+        for arena, pieces in groups:
+            bad += arena.token_windows(pieces, x_ptr, y_ptr, batch, seq_len,
+                                       sc, dc, vocab_size)
+        for off, row, j0, n in slow:
+            raw = self.pread(off, n * ss)
+            if len(raw) != n * ss:
+                raise err.OutOfRange(
+                    f"token read at {off}: short read ({len(raw)} bytes)")
+            out = native.token_convert_host(raw, sc, dc, n)
+            nx = min(j0 + n, seq_len) - j0      # tokens j < seq_len
+            if nx > 0:
+                self._land(out[:nx * ds], x_ptr + (row * seq_len + j0) * ds,
+                           dst_on_device)
+            y0 = max(j0, 1)                     # tokens j >= 1
+            if j0 + n > y0:
+                self._land(out[(y0 - j0) * ds:],
+                           y_ptr + (row * seq_len + y0 - 1) * ds,
+                           dst_on_device)
+            if vocab_size > 0:
+                bad += sum(1 for v in memoryview(raw).cast(fmt)
+                           if v < 0 or v >= vocab_size)
+        return bad
+
     @staticmethod
     def _land(out: bytes, dptr: int, dst_on_device: bool) -> None:
         import ctypes

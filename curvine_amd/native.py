@@ -211,6 +211,30 @@ class Arena:
         if block:
             self._n.arena_block_store_ptr(self.handle, block)
 
+    def token_windows(self, pieces: list[tuple[int, int, int, int]],
+                      x_ptr: int, y_ptr: int, batch: int, seq_len: int,
+                      src_dtype: int, dst_dtype: int,
+                      vocab_size: int = 0) -> int:
+        """Token-window gather: `batch` windows of seq_len + 1 tokens each
+        become x = w[:-1] and y = w[1:], two dense [batch, seq_len] arrays
+        of dst_dtype at `x_ptr` and `y_ptr`.  Each piece (src_off, row, j0,
+        n) holds n >= 1 consecutive src_dtype tokens at arena byte src_off
+        (any alignment): tokens j0 .. j0+n-1 of window `row`.  Token j
+        lands at x[row, j] when j < seq_len and at y[row, j - 1] when
+        j >= 1, widened (see token_windows_supported; codes from DTYPES).
+        Device arena + device destinations = one token_windows_kernel
+        launch, synchronised on return; host arena + host destinations =
+        the same scalar routines in C++.
+
+        With vocab_size > 0 returns how many tokens read lie outside
+        [0, vocab_size) (a token two windows share counts twice); they are
+        still written.  vocab_size 0 checks nothing and returns 0.  Bad
+        pairs, pieces, ranges, alignment and destinations on the wrong
+        side raise ValueError before anything runs."""
+        return self._n.arena_token_windows(self.handle, pieces, x_ptr, y_ptr,
+                                           batch, seq_len, src_dtype,
+                                           dst_dtype, vocab_size)
+
     def lz4_compress(self, off: int, n: int) -> bytes:
         """Compress arena bytes [off, off+n) into a CVLZ container (HIP
         kernel on device arenas: only compressed bytes cross D2H; host
@@ -424,6 +448,25 @@ def block_convert_host(buf, src_dtype: int, dst_dtype: int, n: int, scales,
     on."""
     return load().block_convert_host(buf, src_dtype, dst_dtype, n, scales,
                                      scale_e0, m, k, bm, bn, scale_g0)
+
+
+# token files: the id dtypes a token window is read from, and the integer
+# dtypes it is widened to (U16/U32 zero-extend, I32 sign-extends)
+TOKEN_SOURCES = ("U16", "U32", "I32")
+TOKEN_TARGETS = ("I32", "I64")
+
+
+def token_windows_supported(src: str, dst: str) -> bool:
+    """Arena.token_windows reads `src` tokens into `dst` tensors.  U32 ->
+    I32 would change values and is refused."""
+    return src in TOKEN_SOURCES and dst in TOKEN_TARGETS and \
+        (src, dst) != ("U32", "I32")
+
+
+def token_convert_host(buf, src_dtype: int, dst_dtype: int, n: int) -> bytes:
+    """Widen `n` packed tokens on the host with the routine the
+    token_windows kernel uses: the widened bytes."""
+    return load().token_convert_host(buf, src_dtype, dst_dtype, n)
 
 
 def convert_host(buf, src_dtype: int, dst_dtype: int, n: int, scales=None,

@@ -1,4 +1,5 @@
 from curvine_amd.sdk.fsspec_fs import CurvineFileSystemSpec  # noqa: F401
 from curvine_amd.sdk.torch_io import read_into_tensor, CurvineTensorReader  # noqa: F401
+from curvine_amd.sdk.dataset import CurvineTokenLoader  # noqa: F401
 from curvine_amd.sdk.safetensors_io import (CurvineSafetensors, TensorInfo,  # noqa: F401
                                             load_file, save_file)
