@@ -154,6 +154,7 @@ static uint32_t crc32c_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
 #include "mx_cast.hip"
 #include "block_cast.hip"
 #include "token_gather.hip"
+#include "token_docs.hip"
 
 // ---------------------------------------------------------------------------
 // GPU availability
@@ -1597,6 +1598,119 @@ static void absmax_scales(int device, std::vector<AbsmaxSegTuple> segs_in) {
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// ---- document structure of a token batch (token_docs.hip) ----
+//
+// x is a dense [rows, seq_len] array of I32 / I64 at x_ptr; pos_ptr and
+// doc_ptr receive position_ids and doc_ids in x's dtype, cu_ptr the int32
+// cu_seqlens (rows * seq_len + 1 entries of room, n_seqs + 1 written); each
+// of the three may be 0, which skips that output.  Returns (n_seqs,
+// max_seqlen).  device >= 0: summary, offsets and write kernels on the
+// caller's thread stream, the chunk table in memory of this call, one D2H
+// copy of the two result words; device == -1: the host loop.  Every
+// argument error is raised before anything runs.
+static std::pair<uint64_t, uint64_t> token_docs(
+    int device, uintptr_t x_ptr, uint64_t rows, uint64_t seq_len, uint64_t dt,
+    int64_t eos_id, uintptr_t pos_ptr, uintptr_t doc_ptr, uintptr_t cu_ptr) {
+  if (device < -1) throw std::invalid_argument("token docs: bad device");
+  if (dt >= DT_COUNT)
+    throw std::invalid_argument("token docs: unknown dtype code");
+  if (dt != DT_I32 && dt != DT_I64)
+    throw std::invalid_argument("token docs: dtype is not I32 / I64");
+  if (rows == 0 || seq_len == 0)
+    throw std::invalid_argument("token docs: rows and seq_len must be positive");
+  uint64_t ds = cast_itemsize((uint32_t)dt);
+  uint64_t n_el, bytes, x_end, pos_end, doc_end, cu_b, cu_end, key_top;
+  // positions and document indices fit the dtype; row keys fit 64 bits
+  if ((dt == DT_I32 && seq_len > (uint64_t)INT32_MAX) ||
+      __builtin_mul_overflow(rows, seq_len, &n_el) ||
+      __builtin_add_overflow(n_el, rows, &key_top) ||
+      __builtin_mul_overflow(n_el, ds, &bytes) ||
+      __builtin_add_overflow((uint64_t)x_ptr, bytes, &x_end) ||
+      __builtin_add_overflow((uint64_t)pos_ptr, bytes, &pos_end) ||
+      __builtin_add_overflow((uint64_t)doc_ptr, bytes, &doc_end) ||
+      __builtin_mul_overflow(n_el + 1, (uint64_t)4, &cu_b) ||
+      __builtin_add_overflow((uint64_t)cu_ptr, cu_b, &cu_end))
+    throw std::invalid_argument("token docs: size overflows");
+  uint64_t cpr = (seq_len + TOKEN_DOC_CHUNK - 1) / TOKEN_DOC_CHUNK, n_chunks;
+  if (__builtin_mul_overflow(rows, cpr, &n_chunks) ||
+      n_chunks > (uint64_t)INT32_MAX)
+    throw std::invalid_argument("token docs: size overflows");
+  if (cu_ptr && n_el >= (1ull << 31))
+    throw std::invalid_argument(
+        "token docs: cu_seqlens needs rows * seq_len below 2^31");
+  if (x_ptr == 0 || x_ptr % ds)
+    throw std::invalid_argument("token docs: x_ptr null or misaligned");
+  if (pos_ptr % ds)
+    throw std::invalid_argument("token docs: pos_ptr misaligned");
+  if (doc_ptr % ds)
+    throw std::invalid_argument("token docs: doc_ptr misaligned");
+  if (cu_ptr % 4)
+    throw std::invalid_argument("token docs: cu_ptr misaligned");
+  if (eos_id < 0 || (dt == DT_I32 && eos_id > (int64_t)INT32_MAX))
+    throw std::invalid_argument(
+        "token docs: eos_id negative or outside the dtype");
+  uint64_t eos = (uint64_t)eos_id;
+  const uint8_t* x = (const uint8_t*)x_ptr;
+  uint8_t* pos = (uint8_t*)pos_ptr;
+  uint8_t* doc = (uint8_t*)doc_ptr;
+  int32_t* cu = (int32_t*)cu_ptr;
+  py::gil_scoped_release rel;
+  unsigned long long result[2] = {0, 0};
+  if (device < 0) {
+    // the host loop dereferences all four: device memory is the wrong side
+    for (uintptr_t p : {x_ptr, pos_ptr, doc_ptr, cu_ptr}) {
+      hipPointerAttribute_t at;
+      if (!p) continue;
+      if (hipPointerGetAttributes(&at, (const void*)p) != hipSuccess) {
+        (void)hipGetLastError();   // plain host memory, or no runtime
+        continue;
+      }
+      if (at.type == hipMemoryTypeDevice)
+        throw std::invalid_argument(
+            "token docs: device pointer with device -1");
+    }
+    uint64_t n_seqs, max_seqlen;
+    token_docs_host(x, rows, seq_len, (uint32_t)ds, eos, pos, doc, cu, n_seqs,
+                    max_seqlen);
+    return {n_seqs, max_seqlen};
+  }
+  HIP_CHECK(hipSetDevice(device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  check_device_range(device, x_ptr, x_end, "token docs", "x_ptr", "source",
+                     known);
+  if (pos_ptr)
+    check_device_range(device, pos_ptr, pos_end, "token docs", "pos_ptr",
+                       "destination", known);
+  if (doc_ptr)
+    check_device_range(device, doc_ptr, doc_end, "token docs", "doc_ptr",
+                       "destination", known);
+  if (cu_ptr)
+    check_device_range(device, cu_ptr, cu_end, "token docs", "cu_ptr",
+                       "destination", known);
+  hipStream_t s = thread_stream(device);
+  size_t room = Scratch::room<unsigned long long>(2) +
+                2 * Scratch::room<uint64_t>(n_chunks);
+  DevFree mem;
+  HIP_CHECK(hipMalloc(&mem.p, room));
+  Scratch sc(mem.p, room);
+  unsigned long long* d_result = sc.take<unsigned long long>(2);
+  uint64_t* d_counts = sc.take<uint64_t>(n_chunks);
+  uint64_t* d_keys = sc.take<uint64_t>(n_chunks);
+  HIP_CHECK(hipMemsetAsync(d_result, 0, sizeof(result), s));
+  launch(token_doc_summary_kernel, (unsigned)n_chunks, WG, s, x, seq_len, cpr,
+         (uint32_t)ds, eos, d_counts, d_keys);
+  launch(token_doc_offsets_kernel, 1u, WG, s, d_counts, d_keys, n_chunks, rows,
+         d_result);
+  launch(token_doc_write_kernel, (unsigned)n_chunks, WG, s, x, rows, seq_len,
+         cpr, (uint32_t)ds, eos, (const uint64_t*)d_counts,
+         (const uint64_t*)d_keys, pos, doc, cu, d_result);
+  HIP_CHECK(hipMemcpyAsync(result, d_result, sizeof(result),
+                           hipMemcpyDeviceToHost, s));
+  // the outputs are complete and the table freed once this returns
+  HIP_CHECK(hipStreamSynchronize(s));
+  return {result[0], result[1]};
+}
+
 // ---- MX tensors: E8M0 block scales, E4M3 / E2M1 elements (mx_cast.hip) ----
 //
 // Entry points of their own beside absmax_scales, store_ptr, convert_ptr
@@ -2840,6 +2954,7 @@ PYBIND11_MODULE(_native, m) {
   m.def("arena_token_windows", &arena_token_windows);
   m.def("token_convert_host", &token_convert_host);
   m.def("absmax_scales", &absmax_scales);
+  m.def("token_docs", &token_docs);
   m.def("arena_mx_store_ptr", &arena_mx_store_ptr);
   m.def("arena_mx_convert_ptr", &arena_mx_convert_ptr);
   m.def("mx_scales", &mx_scales);
@@ -2925,5 +3040,6 @@ PYBIND11_MODULE(_native, m) {
   m.attr("CRC_SUB") = CRC_SUB;
   m.attr("CAST_TILE") = CAST_TILE;
   m.attr("TOKEN_TILE") = TOKEN_TILE;
+  m.attr("TOKEN_DOC_CHUNK") = TOKEN_DOC_CHUNK;
   m.attr("__hip_arch__") = "gfx950";
 }

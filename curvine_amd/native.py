@@ -469,6 +469,27 @@ def token_convert_host(buf, src_dtype: int, dst_dtype: int, n: int) -> bytes:
     return load().token_convert_host(buf, src_dtype, dst_dtype, n)
 
 
+def token_docs(device: int, x_ptr: int, rows: int, seq_len: int, dtype: int,
+               eos_id: int, pos_ptr: int = 0, doc_ptr: int = 0,
+               cu_ptr: int = 0) -> tuple[int, int]:
+    """Document structure of x, a dense [rows, seq_len] array of I32 / I64
+    ids at x_ptr, under the end-of-document id `eos_id` (a token equal to it
+    ends its document and belongs to it).  For row r, column t:
+    doc_ids[r, t] counts the eos in columns < t; position_ids[r, t] is
+    t - start with start one past the last eos in columns < t, or 0; flat
+    index r * seq_len + t starts a sequence iff t == 0 or x[r, t-1] is eos.
+    pos_ptr / doc_ptr receive position_ids / doc_ids in x's dtype; cu_ptr
+    (room for rows * seq_len + 1 int32, rows * seq_len < 2**31) receives the
+    ascending starts followed by rows * seq_len, n_seqs + 1 entries.  Each of
+    the three may be 0: that output is skipped.  Returns (n_seqs,
+    max_seqlen), the number of starts and the longest sequence.  device >=
+    0: three launches (chunk summaries, offsets, write) on that GPU,
+    synchronised on return; device == -1: the same routines in C++ over host
+    memory.  Bad arguments raise ValueError before anything runs."""
+    return tuple(load().token_docs(device, x_ptr, rows, seq_len, dtype,
+                                   eos_id, pos_ptr, doc_ptr, cu_ptr))
+
+
 def convert_host(buf, src_dtype: int, dst_dtype: int, n: int, scales=None,
                  scale_every: int = 0, scale_e0: int = 0) -> bytes:
     """Convert `n` packed elements on the host with the kernel's own

@@ -1,3 +1,6 @@
+"""User-facing SDK: fsspec cv://, torch reads, safetensors load / save, and
+CurvineTokenLoader (token-window batches; with `eos_id` and `documents` also
+position ids, doc ids and cu_seqlens per batch)."""
 from curvine_amd.sdk.fsspec_fs import CurvineFileSystemSpec  # noqa: F401
 from curvine_amd.sdk.torch_io import read_into_tensor, CurvineTensorReader  # noqa: F401
 from curvine_amd.sdk.dataset import CurvineTokenLoader  # noqa: F401

@@ -15,7 +15,9 @@ HBM tier:
   tensor per batch.
 * `CurvineTokenLoader` — flat token-id files (uint16 / uint32 / int32):
   windows of seq_len + 1 ids become the (x, y) tensors of a language-model
-  step in one kernel launch per batch, with a vocabulary check.
+  step in one kernel launch per batch, with a vocabulary check; on request
+  also position ids, document ids and cu_seqlens under an end-of-document
+  id (native.token_docs).
 
 Multiprocess loading: pass ``worker_init_fn=curvine_worker_init`` so each
 DataLoader worker builds its own client connection (connections must not
@@ -250,7 +252,12 @@ class CurvineDeviceLoader:
 # HBM-tier files one token_windows_kernel launch reads each window once from
 # the arena and writes both tensors, widened, counting ids outside the
 # vocabulary on the way; no raw-byte tensor, no widen or slice kernels.
+# Corpora are documents joined by an end-of-document id: native.token_docs
+# derives position ids, document ids and cu_seqlens from the finished x.
 # ---------------------------------------------------------------------------
+
+TOKEN_DOCUMENT_OUTPUTS = ("position_ids", "doc_ids", "cu_seqlens")
+
 
 class CurvineTokenLoader:
     """Batches of token windows: yields (x, y), two contiguous
@@ -272,6 +279,19 @@ class CurvineTokenLoader:
     wrong dtype or header size shows up here, not as an illegal access
     inside the embedding kernel.
 
+    With ``documents``, any subset of ("position_ids", "doc_ids",
+    "cu_seqlens"), and ``eos_id`` the loader yields (x, y, docs): a token
+    equal to eos_id ends its document and belongs to it, and docs holds the
+    requested tensors on ``device``, derived from x by one
+    native.token_docs call per batch.  position_ids and doc_ids are
+    [B, seq_len] of ``out_dtype``: positions restart at 0 after every
+    eos_id (a window that begins mid-document counts from 0), doc_ids count
+    the eos_id before each token in its row.  cu_seqlens is int32: the flat
+    indices where a sequence starts (column 0 of every row and the token
+    after every eos_id) followed by B * seq_len, n_seqs + 1 entries; it is
+    a view of a B * seq_len + 1 buffer.  With it docs also holds
+    "max_seqlen", an int.  y is not masked at document boundaries.
+
     HBM-tier files + cuda device = the device kernel; MEM tier + cpu
     device = its host twin; anything else (file tier, MEM tier + cuda
     device, tokens cut by a block boundary) goes through pread and the
@@ -284,7 +304,8 @@ class CurvineTokenLoader:
                  header_bytes: int = 0, stride: int | None = None,
                  shuffle: bool = False, seed: int = 0,
                  drop_last: bool = True, rank: int = 0, world: int = 1,
-                 vocab_size: int = 0):
+                 vocab_size: int = 0, eos_id: int | None = None,
+                 documents: tuple[str, ...] = ()):
         import torch
 
         from curvine_amd import errors as err
@@ -311,6 +332,29 @@ class CurvineTokenLoader:
             raise err.InvalidArgument("token loader: negative header_bytes")
         if vocab_size < 0:
             raise err.InvalidArgument("token loader: negative vocab_size")
+        documents = tuple(documents)
+        for name in documents:
+            if name not in TOKEN_DOCUMENT_OUTPUTS:
+                raise err.InvalidArgument(
+                    f"token loader: unknown documents output {name!r}")
+        if documents and eos_id is None:
+            raise err.InvalidArgument(
+                "token loader: documents need an eos_id")
+        if eos_id is not None:
+            if not isinstance(eos_id, int) or eos_id < 0:
+                raise err.InvalidArgument(
+                    "token loader: eos_id must be a non-negative integer")
+            if vocab_size > 0 and eos_id >= vocab_size:
+                raise err.InvalidArgument(
+                    f"token loader: eos_id {eos_id} outside "
+                    f"[0, {vocab_size})")
+            if eos_id > torch.iinfo(out_dtype).max:
+                raise err.InvalidArgument(
+                    f"token loader: eos_id {eos_id} does not fit {out_dtype}")
+        if "cu_seqlens" in documents and batch_size * seq_len >= 2 ** 31:
+            raise err.InvalidArgument(
+                "token loader: cu_seqlens needs batch_size * seq_len "
+                "below 2**31")
         self.device = device
         self.seq_len = seq_len
         self.batch_size = batch_size
@@ -323,6 +367,8 @@ class CurvineTokenLoader:
         self.rank = rank
         self.world = world
         self.vocab_size = vocab_size
+        self.eos_id = eos_id
+        self.documents = documents
         self.epoch = 0
         self._fs = SyncFs(conf)
         self._readers = []
@@ -395,8 +441,13 @@ class CurvineTokenLoader:
         import torch
 
         from curvine_amd import errors as err
+        from curvine_amd import native
         dev = torch.device(self.device)
         on_dev = dev.type != "cpu"
+        dev_index = -1
+        if on_dev:
+            dev_index = torch.cuda.current_device() if dev.index is None \
+                else dev.index
         key = (self.epoch if self.shuffle else None, on_dev)
         if self._plans is None or self._plans[0] != key:
             self._plans = (key, self._plan(on_dev))
@@ -413,7 +464,30 @@ class CurvineTokenLoader:
                 raise err.InvalidArgument(
                     f"token loader: {bad} token ids outside "
                     f"[0, {self.vocab_size}) in batch {b}")
-            yield x, y
+            if not self.documents:
+                yield x, y
+                continue
+            # x is complete: every exec_token_windows call has returned
+            docs = {}
+            ptrs = {}
+            for name in self.documents:
+                if name == "cu_seqlens":
+                    t = torch.empty(rows * T + 1, dtype=torch.int32,
+                                    device=dev)
+                else:
+                    t = torch.empty((rows, T), dtype=self.out_dtype,
+                                    device=dev)
+                docs[name] = t
+                ptrs[name] = t.data_ptr()
+            n_seqs, max_seqlen = native.token_docs(
+                dev_index, x.data_ptr(), rows, T,
+                native.DTYPES[self.dst_dtype], self.eos_id,
+                ptrs.get("position_ids", 0), ptrs.get("doc_ids", 0),
+                ptrs.get("cu_seqlens", 0))
+            if "cu_seqlens" in docs:
+                docs["cu_seqlens"] = docs["cu_seqlens"][:n_seqs + 1]
+                docs["max_seqlen"] = max_seqlen
+            yield x, y, docs
 
     def close(self) -> None:
         for r in self._readers:

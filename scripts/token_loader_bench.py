@@ -14,6 +14,16 @@ Needs a GPU: without one it stops, unless --rehearse asks for a tiny
 host-memory walk through the same code that measures nothing.
 
     python scripts/token_loader_bench.py [--out profiles/token_loader.json]
+
+With --docs the comparison is the document outputs instead: the loader
+yielding (x, y, docs) with position_ids, doc_ids and cu_seqlens (one
+native.token_docs call per batch: three launches) against the loader
+yielding (x, y) followed by the torch expression for the same three outputs
+on the GPU (eq, cumsum, cummax, nonzero, cat, diff, max).  The files carry
+the eos id at about one token in 500.  The plain (x, y) batch time of the
+same run is recorded beside both.
+
+    python scripts/token_loader_bench.py --docs [--out profiles/token_docs.json]
 """
 import argparse
 import json
@@ -26,6 +36,86 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 SHAPES = [("U16", 8), ("U16", 64), ("U32", 64)]
+EOS = 1                                     # --docs: the end-of-document id
+EOS_EVERY = 500
+DOCS = ("position_ids", "doc_ids", "cu_seqlens")
+
+
+def torch_docs(torch, x, eos):
+    """The three document outputs of x as a chain of torch ops."""
+    rows, T = x.shape
+    is_eos = x == eos
+    ind = is_eos.to(x.dtype)
+    doc = torch.cumsum(ind, 1) - ind
+    shifted = torch.zeros_like(is_eos)
+    shifted[:, 1:] = is_eos[:, :-1]
+    col = torch.arange(T, dtype=x.dtype, device=x.device).expand(rows, T)
+    start = torch.cummax(torch.where(shifted, col, 0), 1).values
+    pos = col - start
+    shifted[:, 0] = True
+    starts = torch.nonzero(shifted.view(-1)).view(-1)
+    end = torch.tensor([rows * T], dtype=starts.dtype, device=x.device)
+    cu = torch.cat([starts, end]).to(torch.int32)
+    return {"position_ids": pos, "doc_ids": doc, "cu_seqlens": cu,
+            "max_seqlen": int(torch.diff(cu).max())}
+
+
+def bench_docs(args, torch, CurvineTokenLoader, cconf, paths, device, sync):
+    """Per shape: (x, y, docs) from the loader against (x, y) from the
+    loader + torch_docs, alternating batch by batch."""
+    import statistics as st
+    T = args.seq_len
+    results = []
+    for src, B in SHAPES:
+        kw = dict(device=device, src_dtype=src, shuffle=True, seed=1)
+        fused = CurvineTokenLoader(cconf, [paths[src]], T, B, eos_id=EOS,
+                                   documents=DOCS, **kw)
+        plain = CurvineTokenLoader(cconf, [paths[src]], T, B, **kw)
+        n_batches = min(len(fused), args.warmup + args.batches)
+        it_f, it_p = iter(fused), iter(plain)
+        first_f, first_p = next(it_f), next(it_p)   # resolves the plans
+        fused_t, plain_t, torch_t = [], [], []
+        for b in range(n_batches):
+            sync()
+            t0 = time.perf_counter()
+            x, y, docs = first_f if b == 0 else next(it_f)
+            sync()
+            t1 = time.perf_counter()
+            px, py = first_p if b == 0 else next(it_p)
+            sync()
+            t2 = time.perf_counter()
+            ref = torch_docs(torch, px, EOS)
+            sync()
+            t3 = time.perf_counter()
+            if b == 0:
+                assert torch.equal(x, px) and torch.equal(y, py)
+                assert all(torch.equal(docs[k], ref[k]) for k in DOCS) and \
+                    docs["max_seqlen"] == ref["max_seqlen"], \
+                    "the two routes disagree"
+                n_seqs = len(ref["cu_seqlens"]) - 1
+            if b >= args.warmup:
+                fused_t.append(t1 - t0)
+                plain_t.append(t2 - t1)
+                torch_t.append(t3 - t1)
+        fused.close()
+        plain.close()
+
+        def stats(ts):
+            return {"mean_us": round(st.mean(ts) * 1e6, 2),
+                    "stdev_us": round(st.stdev(ts) * 1e6, 2)
+                    if len(ts) > 1 else None,
+                    "min_us": round(min(ts) * 1e6, 2),
+                    "batches_us": [round(t * 1e6, 1) for t in ts]}
+        results.append({
+            "src_dtype": src, "out_dtype": "I64", "seq_len": T, "batch": B,
+            "eos_every": EOS_EVERY, "n_seqs_first_batch": n_seqs,
+            "timed_batches": len(fused_t), "warmup_batches": args.warmup,
+            "loader_with_documents": stats(fused_t),
+            "loader_then_torch": stats(torch_t),
+            "loader_plain_xy": stats(plain_t),
+            "outputs_equal": True})
+        print(json.dumps(results[-1]), flush=True)
+    return results
 
 
 def main():
@@ -34,10 +124,15 @@ def main():
     p.add_argument("--seq-len", type=int, default=4096)
     p.add_argument("--batches", type=int, default=20)
     p.add_argument("--warmup", type=int, default=5)
-    p.add_argument("--out", default="profiles/token_loader.json")
+    p.add_argument("--out", default=None)
+    p.add_argument("--docs", action="store_true",
+                   help="time the document outputs against torch ops")
     p.add_argument("--rehearse", action="store_true",
                    help="tiny MEM-tier run on the CPU; writes no profile")
     args = p.parse_args()
+    if args.out is None:
+        args.out = "profiles/token_docs.json" if args.docs \
+            else "profiles/token_loader.json"
 
     import numpy as np
     import torch
@@ -83,6 +178,9 @@ def main():
     for src in ("U16", "U32"):
         n = (args.file_mb << 20) // np.dtype(np_dt[src]).itemsize
         toks = rng.integers(0, vocab[src], n, dtype=np_dt[src])
+        if args.docs:
+            toks[toks == EOS] = EOS + 1
+            toks[rng.integers(0, EOS_EVERY, n) == 0] = EOS
         paths[src] = f"/tokens/{src}.bin"
         sf.write_file(paths[src], toks.tobytes(), storage_tier=tier)
         del toks
@@ -110,8 +208,9 @@ def main():
                 & 0xFFFFFFFF
         return w[:, :-1].contiguous(), w[:, 1:].contiguous()
 
-    results = []
-    for src, B in SHAPES:
+    results = bench_docs(args, torch, CurvineTokenLoader, cconf, paths,
+                         device, sync) if args.docs else []
+    for src, B in ([] if args.docs else SHAPES):
         item = native.DTYPE_ITEMSIZE[src]
         ld = CurvineTokenLoader(cconf, [paths[src]], T, B, device=device,
                                 src_dtype=src, shuffle=True, seed=1)
@@ -180,6 +279,13 @@ def main():
                         "at both ends; routes alternate per batch",
               "parent_widen": "unsigned cast" if unsigned_cast
               else "signed cast + mask", "results": results}
+    if args.docs:
+        del report["parent_widen"]
+        report.update(
+            bench="token_docs", eos_id=EOS,
+            timing="host clock around one batch, device synchronised at "
+                   "both ends; routes alternate per batch; "
+                   "loader_then_torch includes its loader_plain_xy batch")
     sf.shutdown()
     smc.stop()
     if args.rehearse:
