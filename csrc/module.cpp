@@ -380,6 +380,21 @@ struct Scratch {
   }
 };
 
+// device memory of one call that is not tied to an arena, carved the same
+// way: allocated here, freed when the call returns (after its last sync)
+struct CallScratch : Scratch {
+  void* mem;
+  static void* alloc(size_t bytes) {
+    void* p = nullptr;
+    HIP_CHECK(hipMalloc(&p, bytes));
+    return p;
+  }
+  explicit CallScratch(size_t bytes) : Scratch(alloc(bytes), bytes), mem(p) {}
+  CallScratch(const CallScratch&) = delete;
+  CallScratch& operator=(const CallScratch&) = delete;
+  ~CallScratch() { (void)hipFree(mem); }
+};
+
 // g_crc_tab / g_comb_mat are per-device symbols: upload once per device,
 // under a lock of their own, so no arena re-uploads them under another
 // arena's running CRC kernel.  Caller has set the device.
@@ -1041,221 +1056,9 @@ static void arena_gather_ptr(
   HIP_CHECK(hipStreamSynchronize(a->kstream));
 }
 
-// ---- typed tensor load (tensor_cast.hip) ----
-//
-// Segments: (src_off, dst_ptr, rows, run, src_pitch, src_dtype, dst_dtype).
-// A 10-tuple appends (scale_ptr, scale_every, scale_e0): F8_E4M3 -> F32/F16/
-// BF16 multiplied by the f32 scale of each element's group.
-// Every argument error is raised here, on the host, before any launch.
-
-// segment fields as they arrive from Python: 7 without, 10 with a scale
-struct SegArgs {
-  uint64_t a, b, rows, run, pitch, sdt, ddt;
-  uint64_t scale_ptr = 0, scale_every = 0, scale_e0 = 0;
-};
-
-typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                   uint64_t> CastSegTuple;
-typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                   uint64_t, uint64_t, uint64_t, uint64_t> ScaledSegTuple;
-typedef std::variant<CastSegTuple, ScaledSegTuple> AnySegTuple;
-
-static SegArgs seg_args(const AnySegTuple& v) {
-  if (auto* t = std::get_if<CastSegTuple>(&v))
-    return {std::get<0>(*t), std::get<1>(*t), std::get<2>(*t), std::get<3>(*t),
-            std::get<4>(*t), std::get<5>(*t), std::get<6>(*t)};
-  auto& t = std::get<ScaledSegTuple>(v);
-  return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t),
-          std::get<4>(t), std::get<5>(t), std::get<6>(t), std::get<7>(t),
-          std::get<8>(t), std::get<9>(t)};
-}
-
-// The scale fields against the dtype pair (codes already range-checked):
-// a quantising pair needs a scale, F8_E4M3 -> F32/F16/BF16 takes one or is
-// the plain upcast, no other pair takes one.  Returns false when the pair
-// is not a scaled one, for the caller's own pair check.
-static bool scale_validate(const std::string& who, const SegArgs& s,
-                           uint64_t total, bool quant_ok, bool dequant_ok) {
-  bool quant = cast_pair_quantizes((uint32_t)s.sdt, (uint32_t)s.ddt);
-  bool dequant = cast_pair_dequantizes((uint32_t)s.sdt, (uint32_t)s.ddt);
-  if (!s.scale_ptr) {
-    if (quant && quant_ok)
-      throw std::invalid_argument(
-          who + ": unsupported dtype pair without a scale_ptr");
-    return false;
-  }
-  if (!((quant && quant_ok) || (dequant && dequant_ok)))
-    throw std::invalid_argument(who + ": scale_ptr on a dtype pair that takes none");
-  if (s.scale_ptr % 4)
-    throw std::invalid_argument(who + ": scale_ptr misaligned");
-  uint64_t last, bytes, end;
-  if (__builtin_add_overflow(s.scale_e0, total, &last) ||
-      __builtin_mul_overflow(s.scale_every ? last / s.scale_every + 1 : 1,
-                             (uint64_t)4, &bytes) ||
-      __builtin_add_overflow(s.scale_ptr, bytes, &end))
-    throw std::invalid_argument(who + ": scale range overflows");
-  return true;
-}
-
-// [first, last) bytes of the scales a validated scaled segment reads
-static std::pair<uint64_t, uint64_t> scale_span(const CastSeg& g) {
-  uint64_t total = g.rows * g.run;
-  uint64_t g0 = cast_group_of(g.scale_every, g.scale_e0, 0);
-  uint64_t g1 = cast_group_of(g.scale_every, g.scale_e0, total - 1);
-  return {g.scale_ptr + g0 * 4, g.scale_ptr + (g1 + 1) * 4};
-}
-
-static CastSeg cast_validate(uint64_t cap, const SegArgs& in,
-                             bool quant_ok = false) {
-  uint64_t src_off = in.a, dst_ptr = in.b, rows = in.rows, run = in.run,
-           pitch = in.pitch, sdt = in.sdt, ddt = in.ddt;
-  if (sdt >= DT_COUNT || ddt >= DT_COUNT)
-    throw std::invalid_argument("convert: unknown dtype code");
-  uint64_t n_el;
-  if (__builtin_mul_overflow(rows, run, &n_el))
-    throw std::invalid_argument("convert: segment size overflows");
-  bool scaled = scale_validate("convert", in, n_el, quant_ok, true);
-  if (sdt != ddt && !scaled &&
-      !cast_pair_converts((uint32_t)sdt, (uint32_t)ddt))
-    throw std::invalid_argument("convert: unsupported dtype pair");
-  uint64_t ss = cast_itemsize((uint32_t)sdt), ds = cast_itemsize((uint32_t)ddt);
-  uint64_t run_b, span, end, total, dst_b;
-  if (__builtin_mul_overflow(run, ss, &run_b) ||
-      __builtin_mul_overflow(rows, run, &total) ||
-      __builtin_mul_overflow(total, ds, &dst_b) ||
-      __builtin_add_overflow(dst_ptr, dst_b, &end))
-    throw std::invalid_argument("convert: segment size overflows");
-  if (total) {
-    // last byte touched: src_off + (rows-1)*pitch + run*ss, overflow-checked
-    if (__builtin_mul_overflow(rows - 1, pitch, &span) ||
-        __builtin_add_overflow(span, run_b, &span) ||
-        __builtin_add_overflow(src_off, span, &end))
-      throw std::invalid_argument("convert: segment range overflows");
-    if (end > cap) throw std::invalid_argument("convert: arena range out of bounds");
-    if (dst_ptr == 0 || dst_ptr % ds)
-      throw std::invalid_argument("convert: dst_ptr null or misaligned");
-  }
-  CastSeg g;
-  g.src_off = src_off; g.dst_ptr = dst_ptr; g.rows = rows; g.run = run;
-  g.src_pitch = pitch; g.src_dt = (uint32_t)sdt; g.dst_dt = (uint32_t)ddt;
-  g.scale_ptr = in.scale_ptr; g.scale_every = in.scale_every;
-  g.scale_e0 = in.scale_e0;
-  if (sdt == ddt) {            // raw copy at any itemsize: flatten to bytes
-    g.run = run_b;
-    g.src_dt = g.dst_dt = DT_U8;
-  }
-  return g;
-}
-
-// a kernel on `device` dereferences [first, last): it has to be memory of
-// that GPU (or pinned host memory), and where the runtime knows the
-// allocation's extent the range has to lie inside it.  `known` holds the
-// allocations already checked in this call: the tensors of a checkpoint
-// mostly share a few allocator blocks, and the runtime queries cost more
-// than the rest of a small call.  Errors read "<who>: <ptr> is not ..." and
-// "<who>: <noun> lives ...".  Caller has set the device.
-static void check_device_range(
-    int device, uint64_t first, uint64_t last, const std::string& who,
-    const char* ptr, const char* noun,
-    std::vector<std::pair<uint64_t, uint64_t>>& known) {
-  for (auto& k : known)
-    if (first >= k.first && last <= k.second) return;
-  hipPointerAttribute_t at;
-  const void* p = (const void*)(uintptr_t)first;
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-    (void)hipGetLastError();
-    throw std::invalid_argument(who + ": " + ptr +
-                                " is not device-visible memory");
-  }
-  if (at.type == hipMemoryTypeDevice && at.device != device)
-    throw std::invalid_argument(who + ": " + noun + " lives on another device");
-  if (at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost &&
-      at.type != hipMemoryTypeManaged)
-    throw std::invalid_argument(who + ": " + ptr +
-                                " is not device-visible memory");
-  hipDeviceptr_t lo;
-  size_t sz;
-  if (hipMemGetAddressRange(&lo, &sz, (hipDeviceptr_t)p) != hipSuccess) {
-    (void)hipGetLastError();   // extent unknown to the runtime: type check only
-    return;
-  }
-  if (last > (uint64_t)(uintptr_t)lo + sz)
-    throw std::invalid_argument(who + ": " + noun +
-                                " runs past its allocation");
-  known.emplace_back((uint64_t)(uintptr_t)lo, (uint64_t)(uintptr_t)lo + sz);
-}
-
-static void check_scales(int device, const char* who, const CastSeg& g,
-                         std::vector<std::pair<uint64_t, uint64_t>>& known) {
-  if (!g.scale_ptr) return;
-  auto span = scale_span(g);
-  check_device_range(device, span.first, span.second, who, "scale_ptr",
-                     "scales", known);
-}
-
-static void arena_convert_ptr(int h, std::vector<AnySegTuple> segs_in) {
-  Arena* a = get_arena(h);
-  std::vector<CastSeg> segs;
-  segs.reserve(segs_in.size());
-  for (auto& t : segs_in) {
-    CastSeg g = cast_validate(a->cap, seg_args(t));
-    if (g.rows * g.run) segs.push_back(g);
-  }
-  if (segs.empty()) return;
-  py::gil_scoped_release rel;
-  if (!a->is_dev()) {
-    for (auto& g : segs) convert_segment_host((const uint8_t*)a->base, g);
-    return;
-  }
-  Tiles tiles = build_tiles(
-      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
-      [&](size_t i) { return cast_tile_elems(segs[i].src_dt, segs[i].dst_dt); },
-      "convert");
-  std::lock_guard<std::mutex> g(a->mu);
-  HIP_CHECK(hipSetDevice(a->device));
-  std::vector<std::pair<uint64_t, uint64_t>> known;
-  for (auto& s : segs) check_scales(a->device, "convert", s, known);
-  Scratch sc(a, tiles.room<CastSeg>(segs.size()));
-  DevTiles<CastSeg> d = upload_tiles(a, sc, segs, tiles);
-  launch(convert_segments_kernel, d.grid(), WG, a->kstream,
-         (const uint8_t*)a->base, d.items, d.tile_item, d.tile_off, d.n_tiles);
-  HIP_CHECK(hipStreamSynchronize(a->kstream));
-}
-
-// host conversion of `n` packed elements (the slow path of the typed
-// reader: file-tier extents and elements straddling a block boundary go
-// through the same scalar routines as the kernel).  With `scales` (a host
-// buffer of the tensor's f32 group scales) also the scaled pairs in both
-// directions: the byte path of the typed writer quantises here.
-static py::bytes convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
-                              uint64_t n, py::object scales,
-                              uint64_t scale_every, uint64_t scale_e0) {
-  py::buffer_info bi = src.request();
-  SegArgs in{0, 0, 1, n, 0, sdt, ddt};
-  py::buffer_info sbi;
-  if (!scales.is_none()) {
-    sbi = py::cast<py::buffer>(scales).request();
-    uint64_t have = (uint64_t)sbi.size * sbi.itemsize / 4, last;
-    if (!sbi.ptr || (uintptr_t)sbi.ptr % 4 || !have)
-      throw std::invalid_argument("convert: scales empty or misaligned");
-    if (n && (__builtin_add_overflow(scale_e0, n - 1, &last) ||
-              (scale_every ? last / scale_every : 0) >= have))
-      throw std::invalid_argument("convert: scales shorter than the groups");
-    in.scale_ptr = (uint64_t)(uintptr_t)sbi.ptr;
-    in.scale_every = scale_every;
-    in.scale_e0 = scale_e0;
-  }
-  uint64_t ds = ddt < DT_COUNT ? cast_itemsize((uint32_t)ddt) : 1;
-  uint64_t out_b;
-  if (__builtin_mul_overflow(n, ds, &out_b) || out_b > (1ull << 40))
-    throw std::invalid_argument("convert: segment size overflows");
-  // 8-byte words: aligned for every destination itemsize
-  std::vector<uint64_t> out(out_b / 8 + 1);
-  in.b = (uint64_t)(uintptr_t)out.data();
-  CastSeg g = cast_validate((uint64_t)bi.size * bi.itemsize, in, true);
-  if (g.rows * g.run) convert_segment_host((const uint8_t*)bi.ptr, g);
-  return py::bytes((const char*)out.data(), out_b);
-}
+// typed tensor load, store and scales over tensor_cast.hip, mx_cast.hip and
+// block_cast.hip, and check_device_range (needs the plumbing above)
+#include "typed_io.cpp"
 
 // ---- token windows (token_gather.hip) ----
 //
@@ -1385,219 +1188,6 @@ static py::bytes token_convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
   return py::bytes((const char*)out.data(), out_b);
 }
 
-// ---- typed tensor store (tensor_cast.hip) ----
-//
-// Segments: (src_ptr, dst_off, rows, run, src_pitch, src_dtype, dst_dtype):
-// the scatter direction of convert.  The source is an absolute address
-// (a torch tensor or a row-strided view of one), the destination dense at
-// dst_off.  Every argument error is raised here, before any launch.
-
-static CastSeg store_validate(uint64_t cap, const SegArgs& in) {
-  uint64_t src_ptr = in.a, dst_off = in.b, rows = in.rows, run = in.run,
-           pitch = in.pitch, sdt = in.sdt, ddt = in.ddt;
-  if (sdt >= DT_COUNT || ddt >= DT_COUNT)
-    throw std::invalid_argument("store: unknown dtype code");
-  uint64_t n_el;
-  if (__builtin_mul_overflow(rows, run, &n_el))
-    throw std::invalid_argument("store: segment size overflows");
-  bool scaled = scale_validate("store", in, n_el, true, false);
-  if (sdt != ddt && !scaled &&
-      !cast_pair_converts((uint32_t)sdt, (uint32_t)ddt))
-    throw std::invalid_argument("store: unsupported dtype pair");
-  uint64_t ss = cast_itemsize((uint32_t)sdt), ds = cast_itemsize((uint32_t)ddt);
-  uint64_t run_b, span, end, total, dst_b;
-  if (__builtin_mul_overflow(run, ss, &run_b) ||
-      __builtin_mul_overflow(rows, run, &total) ||
-      __builtin_mul_overflow(total, ds, &dst_b) ||
-      __builtin_add_overflow(dst_off, dst_b, &end))
-    throw std::invalid_argument("store: segment size overflows");
-  if (end > cap) throw std::invalid_argument("store: arena range out of bounds");
-  if (total) {
-    // last source byte: src_ptr + (rows-1)*pitch + run*ss, overflow-checked
-    if (__builtin_mul_overflow(rows - 1, pitch, &span) ||
-        __builtin_add_overflow(span, run_b, &span) ||
-        __builtin_add_overflow(src_ptr, span, &end))
-      throw std::invalid_argument("store: source range overflows");
-    if (src_ptr == 0 || src_ptr % ss)
-      throw std::invalid_argument("store: src_ptr null or misaligned");
-    if (dst_off % ds)
-      throw std::invalid_argument("store: dst_off misaligned");
-  }
-  CastSeg g;
-  g.src_off = src_ptr; g.dst_ptr = dst_off; g.rows = rows; g.run = run;
-  g.src_pitch = pitch; g.src_dt = (uint32_t)sdt; g.dst_dt = (uint32_t)ddt;
-  g.scale_ptr = in.scale_ptr; g.scale_every = in.scale_every;
-  g.scale_e0 = in.scale_e0;
-  if (sdt == ddt) {            // raw copy at any itemsize: flatten to bytes
-    g.run = run_b;
-    g.src_dt = g.dst_dt = DT_U8;
-  }
-  return g;
-}
-
-// a device arena's kernel dereferences the source (check_device_range)
-static void store_check_source(
-    Arena* a, const CastSeg& g,
-    std::vector<std::pair<uint64_t, uint64_t>>& known) {
-  uint64_t first = g.src_off;
-  uint64_t last = first + (g.rows - 1) * g.src_pitch +
-                  g.run * cast_itemsize(g.src_dt);   // validated: no overflow
-  check_device_range(a->device, first, last, "store", "src_ptr", "source",
-                     known);
-  check_scales(a->device, "store", g, known);
-}
-
-static void arena_store_ptr(int h, std::vector<AnySegTuple> segs_in) {
-  Arena* a = get_arena(h);
-  std::vector<CastSeg> segs;
-  segs.reserve(segs_in.size());
-  for (auto& t : segs_in) {
-    CastSeg g = store_validate(a->cap, seg_args(t));
-    if (g.rows * g.run) segs.push_back(g);
-  }
-  if (segs.empty()) return;
-  py::gil_scoped_release rel;
-  if (!a->is_dev()) {
-    for (auto& g : segs) store_segment_host((uint8_t*)a->base, g);
-    return;
-  }
-  Tiles tiles = build_tiles(
-      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
-      [&](size_t i) { return cast_tile_elems(segs[i].src_dt, segs[i].dst_dt); },
-      "store");
-  std::lock_guard<std::mutex> g(a->mu);
-  HIP_CHECK(hipSetDevice(a->device));
-  std::vector<std::pair<uint64_t, uint64_t>> known;
-  for (auto& s : segs) store_check_source(a, s, known);
-  Scratch sc(a, tiles.room<CastSeg>(segs.size()));
-  DevTiles<CastSeg> d = upload_tiles(a, sc, segs, tiles);
-  launch(store_segments_kernel, d.grid(), WG, a->kstream,
-         (uint8_t*)a->base, d.items, d.tile_item, d.tile_off, d.n_tiles);
-  // the sources are the caller's to free or overwrite once this returns
-  HIP_CHECK(hipStreamSynchronize(a->kstream));
-}
-
-// ---- group scales for the quantising store (tensor_cast.hip) ----
-//
-// Segments: (src_ptr, rows, run, src_pitch, src_dtype, out_ptr, scale_every,
-// scale_e0, n_groups).  out_ptr[0:n_groups] are the f32 scales of the
-// segment's tensor; they are zeroed, receive each group's amax, and become
-// max(amax, 2^-40) / 448.  Segments may share slots (a tensor given in
-// pieces).  Not tied to an arena: a checkpoint's scales are needed before
-// its first block is placed.  device >= 0: absmax_segments_kernel on the
-// caller's thread stream, tables in memory of this call; device == -1: the
-// host loop.  Every argument error is raised before any launch.
-
-typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                   uint64_t, uint64_t, uint64_t> AbsmaxSegTuple;
-
-struct DevFree {
-  void* p = nullptr;
-  ~DevFree() { if (p) (void)hipFree(p); }
-};
-
-// each slot is zeroed and finished once, however the segments share them
-static std::vector<ScaleSlots> merge_scale_slots(std::vector<ScaleSlots> slots) {
-  std::sort(slots.begin(), slots.end(),
-            [](const ScaleSlots& x, const ScaleSlots& y) { return x.ptr < y.ptr; });
-  std::vector<ScaleSlots> merged;
-  for (auto& r : slots) {
-    if (!merged.empty() && r.ptr <= merged.back().ptr + merged.back().n * 4) {
-      uint64_t end = std::max(merged.back().ptr + merged.back().n * 4,
-                              r.ptr + r.n * 4);
-      merged.back().n = (end - merged.back().ptr) / 4;
-    } else {
-      merged.push_back(r);
-    }
-  }
-  return merged;
-}
-
-static void absmax_scales(int device, std::vector<AbsmaxSegTuple> segs_in) {
-  if (device < -1) throw std::invalid_argument("absmax: bad device");
-  std::vector<AbsmaxSeg> segs;
-  std::vector<ScaleSlots> slots;
-  segs.reserve(segs_in.size());
-  for (auto& t : segs_in) {
-    uint64_t src = std::get<0>(t), rows = std::get<1>(t), run = std::get<2>(t),
-             pitch = std::get<3>(t), sdt = std::get<4>(t),
-             out = std::get<5>(t), every = std::get<6>(t),
-             e0 = std::get<7>(t), n_groups = std::get<8>(t);
-    if (sdt > DT_BF16)
-      throw std::invalid_argument("absmax: source dtype is not F32/F16/BF16");
-    uint64_t ss = cast_itemsize((uint32_t)sdt);
-    uint64_t run_b, total, span, end, last, out_b;
-    if (__builtin_mul_overflow(run, ss, &run_b) ||
-        __builtin_mul_overflow(rows, run, &total) ||
-        __builtin_add_overflow(e0, total, &last) ||
-        __builtin_mul_overflow(n_groups, (uint64_t)4, &out_b) ||
-        __builtin_add_overflow(out, out_b, &end))
-      throw std::invalid_argument("absmax: segment size overflows");
-    if (n_groups == 0 || out == 0 || out % 4)
-      throw std::invalid_argument("absmax: out_ptr null, misaligned or empty");
-    if (total) {
-      if (__builtin_mul_overflow(rows - 1, pitch, &span) ||
-          __builtin_add_overflow(span, run_b, &span) ||
-          __builtin_add_overflow(src, span, &end))
-        throw std::invalid_argument("absmax: source range overflows");
-      if (src == 0 || src % ss)
-        throw std::invalid_argument("absmax: src_ptr null or misaligned");
-      if ((every ? (last - 1) / every : 0) >= n_groups)
-        throw std::invalid_argument("absmax: groups pass n_groups");
-      AbsmaxSeg g;
-      g.src_ptr = src; g.rows = rows; g.run = run; g.src_pitch = pitch;
-      g.out_ptr = out; g.scale_every = every; g.scale_e0 = e0;
-      g.src_dt = (uint32_t)sdt; g.pad = 0;
-      segs.push_back(g);
-    }
-    slots.push_back({out, n_groups});
-  }
-  if (slots.empty()) return;
-  std::vector<ScaleSlots> merged = merge_scale_slots(std::move(slots));
-  py::gil_scoped_release rel;
-  if (device < 0) {
-    for (auto& r : merged) scale_slots_host(r, false);
-    for (auto& g : segs) absmax_segment_host(g);
-    for (auto& r : merged) scale_slots_host(r, true);
-    return;
-  }
-  Tiles tiles = build_tiles(
-      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
-      [](size_t) { return (uint64_t)CAST_TILE; }, "absmax");
-  HIP_CHECK(hipSetDevice(device));
-  std::vector<std::pair<uint64_t, uint64_t>> known;
-  for (auto& g : segs)
-    check_device_range(device, g.src_ptr,
-                       g.src_ptr + (g.rows - 1) * g.src_pitch +
-                           g.run * cast_itemsize(g.src_dt),
-                       "absmax", "src_ptr", "source", known);
-  for (auto& r : merged)
-    check_device_range(device, r.ptr, r.ptr + r.n * 4, "absmax", "out_ptr",
-                       "scales", known);
-  hipStream_t s = thread_stream(device);
-  size_t room = tiles.room<AbsmaxSeg>(segs.size()) +
-                Scratch::room<ScaleSlots>(merged.size());
-  DevFree mem;
-  HIP_CHECK(hipMalloc(&mem.p, room));
-  Scratch sc(mem.p, room);
-  ScaleSlots* d_slots = sc.take<ScaleSlots>(merged.size());
-  HIP_CHECK(hipMemcpyAsync(d_slots, merged.data(),
-                           merged.size() * sizeof(ScaleSlots),
-                           hipMemcpyHostToDevice, s));
-  unsigned slot_grid = (unsigned)std::min<size_t>(merged.size(), 8192);
-  launch(scale_slots_kernel, slot_grid, WG, s, (const ScaleSlots*)d_slots,
-         (uint32_t)merged.size(), 0);
-  if (!tiles.empty()) {
-    DevTiles<AbsmaxSeg> d = upload_tiles(s, sc, segs, tiles);
-    launch(absmax_segments_kernel, d.grid(), WG, s, d.items, d.tile_item,
-           d.tile_off, d.n_tiles);
-  }
-  launch(scale_slots_kernel, slot_grid, WG, s, (const ScaleSlots*)d_slots,
-         (uint32_t)merged.size(), 1);
-  // the scales are read and the tables freed once this returns
-  HIP_CHECK(hipStreamSynchronize(s));
-}
-
 // ---- document structure of a token batch (token_docs.hip) ----
 //
 // x is a dense [rows, seq_len] array of I32 / I64 at x_ptr; pos_ptr and
@@ -1688,11 +1278,8 @@ static std::pair<uint64_t, uint64_t> token_docs(
     check_device_range(device, cu_ptr, cu_end, "token docs", "cu_ptr",
                        "destination", known);
   hipStream_t s = thread_stream(device);
-  size_t room = Scratch::room<unsigned long long>(2) +
-                2 * Scratch::room<uint64_t>(n_chunks);
-  DevFree mem;
-  HIP_CHECK(hipMalloc(&mem.p, room));
-  Scratch sc(mem.p, room);
+  CallScratch sc(Scratch::room<unsigned long long>(2) +
+                 2 * Scratch::room<uint64_t>(n_chunks));
   unsigned long long* d_result = sc.take<unsigned long long>(2);
   uint64_t* d_counts = sc.take<uint64_t>(n_chunks);
   uint64_t* d_keys = sc.take<uint64_t>(n_chunks);
@@ -1709,568 +1296,6 @@ static std::pair<uint64_t, uint64_t> token_docs(
   // the outputs are complete and the table freed once this returns
   HIP_CHECK(hipStreamSynchronize(s));
   return {result[0], result[1]};
-}
-
-// ---- MX tensors: E8M0 block scales, E4M3 / E2M1 elements (mx_cast.hip) ----
-//
-// Entry points of their own beside absmax_scales, store_ptr, convert_ptr
-// and convert_host; the dtype codes of those stay as they are.  A segment
-// names its high-precision side (F32/F16/BF16) and its stored side
-// (F8_E4M3, or F4 = code 17) and carries (scale_ptr, scale_e0, scale_pitch,
-// 32): the element in row r, column c uses the E8M0 byte at
-// scale_ptr[(scale_e0 + r * scale_pitch + c) / 32].  Every argument error
-// is raised on the host before any launch.
-
-enum MxKind { MX_SCALES, MX_STORE, MX_LOAD };
-
-struct MxArgs {
-  uint64_t a, b, rows, run, pitch, hp_dt, stored_dt, scale_ptr, scale_e0,
-      scale_pitch, block;
-};
-
-typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                   uint64_t, uint64_t, uint64_t, uint64_t, uint64_t> MxSegTuple;
-
-// kind MX_SCALES / MX_STORE: a = absolute source; MX_STORE: b = arena
-// offset; MX_LOAD: a = arena offset, b = absolute destination
-static MxSeg mx_validate(const std::string& who, MxKind kind, uint64_t cap,
-                         const MxArgs& in) {
-  if (in.block != MX_BLOCK)
-    throw std::invalid_argument(who + ": block size is not 32");
-  if (in.hp_dt > DT_BF16)
-    throw std::invalid_argument(who + ": not F32/F16/BF16 on the wide side");
-  if (in.stored_dt != DT_F8_E4M3 && in.stored_dt != DT_F4)
-    throw std::invalid_argument(who + ": stored dtype is not F8_E4M3 or F4");
-  uint32_t fmt = in.stored_dt == DT_F4 ? MX_E2M1 : MX_E4M3;
-  uint64_t hs = cast_itemsize((uint32_t)in.hp_dt), bits = mx_bits(fmt);
-  uint64_t ss = kind == MX_LOAD ? 1 : hs;            // source alignment
-  uint64_t total, run_b, q_b, hp_b, span, end, last;
-  if (__builtin_mul_overflow(in.rows, in.run, &total) ||
-      __builtin_mul_overflow(total, hs, &hp_b) ||
-      __builtin_mul_overflow(in.run, kind == MX_LOAD ? bits : hs * 8, &run_b))
-    throw std::invalid_argument(who + ": segment size overflows");
-  run_b /= 8;
-  q_b = total / 8 * bits + total % 8 * bits / 8;
-  uint64_t odd = in.run | in.scale_e0 | (in.rows > 1 ? in.scale_pitch : 0);
-  if (fmt == MX_E2M1 && (odd & 1))
-    throw std::invalid_argument(who + ": F4 piece splits a byte");
-  if (kind == MX_SCALES && (odd % MX_BLOCK))
-    throw std::invalid_argument(who + ": not whole blocks of 32");
-  MxSeg g;
-  g.src = in.a; g.dst = in.b; g.rows = in.rows; g.run = in.run;
-  g.src_pitch = in.pitch; g.scale_ptr = in.scale_ptr;
-  g.scale_e0 = in.scale_e0; g.scale_pitch = in.scale_pitch;
-  g.dt = (uint32_t)in.hp_dt; g.fmt = fmt;
-  if (!total) return g;
-  if (!in.scale_ptr) throw std::invalid_argument(who + ": scale_ptr is null");
-  if (__builtin_mul_overflow(in.rows - 1, in.scale_pitch, &last) ||
-      __builtin_add_overflow(last, in.run, &last) ||
-      __builtin_add_overflow(last, in.scale_e0, &last) ||
-      __builtin_add_overflow(in.scale_ptr, last / MX_BLOCK + 1, &end))
-    throw std::invalid_argument(who + ": scale range overflows");
-  if (__builtin_mul_overflow(in.rows - 1, in.pitch, &span) ||
-      __builtin_add_overflow(span, run_b, &span) ||
-      __builtin_add_overflow(in.a, span, &end))
-    throw std::invalid_argument(who + ": source range overflows");
-  if (in.rows > 1 && in.pitch < run_b)
-    throw std::invalid_argument(who + ": rows overlap");
-  if (kind == MX_LOAD) {
-    if (end > cap) throw std::invalid_argument(who + ": arena range out of bounds");
-    if (in.b == 0 || in.b % hs || __builtin_add_overflow(in.b, hp_b, &end))
-      throw std::invalid_argument(who + ": dst_ptr null, misaligned or overflowing");
-  } else {
-    if (in.a == 0 || in.a % ss)
-      throw std::invalid_argument(who + ": src_ptr null or misaligned");
-    if (kind == MX_STORE &&
-        (__builtin_add_overflow(in.b, q_b, &end) || end > cap))
-      throw std::invalid_argument(who + ": arena range out of bounds");
-  }
-  return g;
-}
-
-static MxArgs mx_args(const MxSegTuple& t) {
-  return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t),
-          std::get<4>(t), std::get<5>(t), std::get<6>(t), std::get<7>(t),
-          std::get<8>(t), std::get<9>(t), std::get<10>(t)};
-}
-
-// [first, last) of the E8M0 bytes a validated segment touches
-static std::pair<uint64_t, uint64_t> mx_scale_span(const MxSeg& g) {
-  uint64_t last = g.scale_e0 + (g.rows - 1) * g.scale_pitch + g.run - 1;
-  return {g.scale_ptr + g.scale_e0 / MX_BLOCK,
-          g.scale_ptr + last / MX_BLOCK + 1};
-}
-
-static void mx_check_ranges(int device, const std::string& who, MxKind kind,
-                            const MxSeg& g,
-                            std::vector<std::pair<uint64_t, uint64_t>>& known) {
-  uint64_t hs = cast_itemsize(g.dt);
-  if (kind == MX_LOAD)
-    check_device_range(device, g.dst, g.dst + g.rows * g.run * hs, who,
-                       "dst_ptr", "destination", known);
-  else
-    check_device_range(device, g.src,
-                       g.src + (g.rows - 1) * g.src_pitch + g.run * hs, who,
-                       "src_ptr", "source", known);
-  auto span = mx_scale_span(g);
-  check_device_range(device, span.first, span.second, who, "scale_ptr",
-                     "scales", known);
-}
-
-// Segments: (src_ptr, dst_off, rows, run, src_pitch, src_dtype, dst_dtype,
-// scale_ptr, scale_e0, scale_pitch, 32), F32/F16/BF16 -> F8_E4M3 or F4.
-static void arena_mx_store_ptr(int h, std::vector<MxSegTuple> segs_in) {
-  Arena* a = get_arena(h);
-  std::vector<MxSeg> segs;
-  segs.reserve(segs_in.size());
-  for (auto& t : segs_in) {
-    MxSeg g = mx_validate("mx store", MX_STORE, a->cap, mx_args(t));
-    if (g.rows * g.run) segs.push_back(g);
-  }
-  if (segs.empty()) return;
-  py::gil_scoped_release rel;
-  if (!a->is_dev()) {
-    for (auto& g : segs)
-      mx_store_segment_host((const uint8_t*)g.src, (uint8_t*)a->base + g.dst, g);
-    return;
-  }
-  Tiles tiles = build_tiles(
-      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
-      [](size_t) { return (uint64_t)CAST_TILE; }, "mx store");
-  std::lock_guard<std::mutex> g(a->mu);
-  HIP_CHECK(hipSetDevice(a->device));
-  std::vector<std::pair<uint64_t, uint64_t>> known;
-  for (auto& s : segs) mx_check_ranges(a->device, "mx store", MX_STORE, s, known);
-  Scratch sc(a, tiles.room<MxSeg>(segs.size()));
-  DevTiles<MxSeg> d = upload_tiles(a, sc, segs, tiles);
-  launch(mx_store_kernel, d.grid(), WG, a->kstream, (uint8_t*)a->base, d.items,
-         d.tile_item, d.tile_off, d.n_tiles);
-  // the sources are the caller's to free or overwrite once this returns
-  HIP_CHECK(hipStreamSynchronize(a->kstream));
-}
-
-// Segments: (src_off, dst_ptr, rows, run, src_pitch, src_dtype, dst_dtype,
-// scale_ptr, scale_e0, scale_pitch, 32), F8_E4M3 or F4 -> F32/F16/BF16.
-static void arena_mx_convert_ptr(int h, std::vector<MxSegTuple> segs_in) {
-  Arena* a = get_arena(h);
-  std::vector<MxSeg> segs;
-  segs.reserve(segs_in.size());
-  for (auto& t : segs_in) {
-    MxArgs in = mx_args(t);
-    std::swap(in.hp_dt, in.stored_dt);     // the tuple is (src, dst) ordered
-    MxSeg g = mx_validate("mx convert", MX_LOAD, a->cap, in);
-    if (g.rows * g.run) segs.push_back(g);
-  }
-  if (segs.empty()) return;
-  py::gil_scoped_release rel;
-  if (!a->is_dev()) {
-    for (auto& g : segs)
-      mx_load_segment_host((const uint8_t*)a->base + g.src, (uint8_t*)g.dst, g);
-    return;
-  }
-  Tiles tiles = build_tiles(
-      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
-      [](size_t) { return (uint64_t)CAST_TILE; }, "mx convert");
-  std::lock_guard<std::mutex> g(a->mu);
-  HIP_CHECK(hipSetDevice(a->device));
-  std::vector<std::pair<uint64_t, uint64_t>> known;
-  for (auto& s : segs) mx_check_ranges(a->device, "mx convert", MX_LOAD, s, known);
-  Scratch sc(a, tiles.room<MxSeg>(segs.size()));
-  DevTiles<MxSeg> d = upload_tiles(a, sc, segs, tiles);
-  launch(mx_load_kernel, d.grid(), WG, a->kstream, (const uint8_t*)a->base,
-         d.items, d.tile_item, d.tile_off, d.n_tiles);
-  HIP_CHECK(hipStreamSynchronize(a->kstream));
-}
-
-// Segments: (src_ptr, rows, run, src_pitch, src_dtype, stored_dtype,
-// out_ptr): the E8M0 bytes of a whole tensor of rows * run elements (run a
-// multiple of 32) land at out_ptr[0 : rows * run / 32].  device >= 0: one
-// mx_scales_kernel launch on the caller's thread stream; -1: the host loop.
-typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                   uint64_t> MxScaleTuple;
-
-static void mx_scales(int device, std::vector<MxScaleTuple> segs_in) {
-  if (device < -1) throw std::invalid_argument("mx scales: bad device");
-  std::vector<MxSeg> segs;
-  segs.reserve(segs_in.size());
-  for (auto& t : segs_in) {
-    MxArgs in{std::get<0>(t), 0, std::get<1>(t), std::get<2>(t),
-              std::get<3>(t), std::get<4>(t), std::get<5>(t), std::get<6>(t),
-              0, std::get<2>(t), MX_BLOCK};
-    MxSeg g = mx_validate("mx scales", MX_SCALES, 0, in);
-    if (g.rows * g.run) segs.push_back(g);
-  }
-  if (segs.empty()) return;
-  py::gil_scoped_release rel;
-  if (device < 0) {
-    for (auto& g : segs) mx_scales_segment_host(g);
-    return;
-  }
-  Tiles tiles = build_tiles(
-      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
-      [](size_t) { return (uint64_t)CAST_TILE; }, "mx scales");
-  HIP_CHECK(hipSetDevice(device));
-  std::vector<std::pair<uint64_t, uint64_t>> known;
-  for (auto& s : segs) mx_check_ranges(device, "mx scales", MX_SCALES, s, known);
-  hipStream_t s = thread_stream(device);
-  size_t room = tiles.room<MxSeg>(segs.size());
-  DevFree mem;
-  HIP_CHECK(hipMalloc(&mem.p, room));
-  Scratch sc(mem.p, room);
-  DevTiles<MxSeg> d = upload_tiles(s, sc, segs, tiles);
-  launch(mx_scales_kernel, d.grid(), WG, s, d.items, d.tile_item, d.tile_off,
-         d.n_tiles);
-  // the scales are read and the tables freed once this returns
-  HIP_CHECK(hipStreamSynchronize(s));
-}
-
-// host conversion of `n` packed elements under the E8M0 bytes in `scales`,
-// element i using scales[(scale_e0 + i) / 32]: quantising when dst_dtype is
-// F8_E4M3 / F4, dequantising when src_dtype is (the byte paths)
-static py::bytes mx_convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
-                                 uint64_t n, py::buffer scales,
-                                 uint64_t scale_e0) {
-  py::buffer_info bi = src.request(), sbi = scales.request();
-  bool quant = sdt <= DT_BF16;
-  MxArgs in{0, 0, 1, n, 0, quant ? sdt : ddt, quant ? ddt : sdt,
-            (uint64_t)(uintptr_t)sbi.ptr, scale_e0, n, MX_BLOCK};
-  uint64_t have = (uint64_t)bi.size * bi.itemsize;
-  std::vector<uint64_t> out;
-  MxSeg g;
-  if (quant) {
-    in.a = (uint64_t)(uintptr_t)bi.ptr;
-    g = mx_validate("mx convert", MX_STORE, ~0ull, in);
-    if (n > have / cast_itemsize(g.dt))
-      throw std::invalid_argument("mx convert: source shorter than n");
-  } else {
-    // a load from a one-row "arena" that is the source buffer; the
-    // destination is this call's own
-    in.b = 8;
-    g = mx_validate("mx convert", MX_LOAD, have, in);
-  }
-  uint64_t last;
-  if (n && (__builtin_add_overflow(scale_e0, n - 1, &last) || !sbi.ptr ||
-            last / MX_BLOCK >= (uint64_t)sbi.size * sbi.itemsize))
-    throw std::invalid_argument("mx convert: scales shorter than the blocks");
-  uint64_t out_b = quant ? n * mx_bits(g.fmt) / 8 : n * cast_itemsize(g.dt);
-  if (out_b > (1ull << 40))
-    throw std::invalid_argument("mx convert: segment size overflows");
-  out.resize(out_b / 8 + 1);
-  if (n) {
-    if (quant)
-      mx_store_segment_host((const uint8_t*)bi.ptr, (uint8_t*)out.data(), g);
-    else
-      mx_load_segment_host((const uint8_t*)bi.ptr, (uint8_t*)out.data(), g);
-  }
-  return py::bytes((const char*)out.data(), out_b);
-}
-
-// ---- 2-D block scales: one F32 scale per bm x bn tile (block_cast.hip) ----
-//
-// Entry points of their own, as the MX ones.  A segment names its
-// high-precision side (F32/F16/BF16) and F8_E4M3 and carries (scale_ptr,
-// scale_e0, scale_pitch, M, K, bm, bn): the element in row r, column c is
-// element t = scale_e0 + r * scale_pitch + c of a tensor (..., M, K) and
-// uses the f32 scale of its tile, block_scale_index(t).  Every argument
-// error is raised on the host before any launch.
-
-enum BlockKind { BLOCK_ABSMAX, BLOCK_STORE, BLOCK_LOAD };
-
-struct BlockArgs {
-  uint64_t a, b, rows, run, pitch, hp_dt, stored_dt, scale_ptr, scale_e0,
-      scale_pitch, M, K, bm, bn;
-};
-
-typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                   uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                   uint64_t, uint64_t> BlockSegTuple;
-
-// [first, last] of the scale indices a segment with elements can meet:
-// the first tile of its first element's row .. the last of its last one's
-static std::pair<uint64_t, uint64_t> block_scale_range(const BlockSeg& g) {
-  uint64_t left;
-  uint64_t tb = g.scale_e0 + (g.rows - 1) * g.scale_pitch + g.run - 1;
-  return {block_scale_index(g, g.scale_e0 / g.K * g.K, left),
-          block_scale_index(g, tb / g.K * g.K + g.K - 1, left)};
-}
-
-// kind BLOCK_ABSMAX / BLOCK_STORE: a = absolute source; BLOCK_STORE: b =
-// arena offset; BLOCK_LOAD: a = arena offset, b = absolute destination.
-// n_scales: how many scales scale_ptr holds, 0 = not known here.
-static BlockSeg block_validate(const std::string& who, BlockKind kind,
-                               uint64_t cap, const BlockArgs& in,
-                               uint64_t n_scales = 0) {
-  if (in.hp_dt > DT_BF16)
-    throw std::invalid_argument(who + ": not F32/F16/BF16 on the wide side");
-  if (in.stored_dt != DT_F8_E4M3)
-    throw std::invalid_argument(who + ": stored dtype is not F8_E4M3");
-  if (!in.M || !in.K || !in.bm || !in.bn)
-    throw std::invalid_argument(who + ": M, K, bm and bn must be positive");
-  uint64_t hs = cast_itemsize((uint32_t)in.hp_dt);
-  uint64_t ss = kind == BLOCK_LOAD ? 1 : hs;         // source itemsize
-  uint64_t total, run_b, hp_b, span, end, last;
-  if (__builtin_mul_overflow(in.rows, in.run, &total) ||
-      __builtin_mul_overflow(total, hs, &hp_b) ||
-      __builtin_mul_overflow(in.run, ss, &run_b))
-    throw std::invalid_argument(who + ": segment size overflows");
-  BlockSeg g;
-  g.src = in.a; g.dst = in.b; g.rows = in.rows; g.run = in.run;
-  g.src_pitch = in.pitch; g.scale_ptr = in.scale_ptr;
-  g.scale_e0 = in.scale_e0; g.scale_pitch = in.scale_pitch;
-  g.M = in.M; g.K = in.K; g.bm = in.bm; g.bn = in.bn;
-  g.tm = (in.M - 1) / in.bm + 1; g.tn = (in.K - 1) / in.bn + 1;
-  g.dt = (uint32_t)in.hp_dt; g.pad = 0;
-  if (!total) return g;
-  if (!in.scale_ptr || in.scale_ptr % 4)
-    throw std::invalid_argument(who + ": scale_ptr null or misaligned");
-  if (in.rows > 1 && in.scale_pitch < in.run)
-    throw std::invalid_argument(who + ": rows overlap in the tensor");
-  uint64_t per_mat, n_mat, hi_b;
-  if (__builtin_mul_overflow(in.rows - 1, in.scale_pitch, &last) ||
-      __builtin_add_overflow(last, in.run, &last) ||
-      __builtin_add_overflow(last, in.scale_e0, &last) ||
-      __builtin_add_overflow(last, in.K, &end) ||
-      __builtin_mul_overflow(g.tm, g.tn, &per_mat) ||
-      __builtin_mul_overflow((last - 1) / in.K / in.M + 1, per_mat, &n_mat) ||
-      __builtin_mul_overflow(n_mat, (uint64_t)4, &hi_b) ||
-      __builtin_add_overflow(in.scale_ptr, hi_b, &end))
-    throw std::invalid_argument(who + ": scale range overflows");
-  if (n_scales && block_scale_range(g).second >= n_scales)
-    throw std::invalid_argument(who + ": tiles pass the scales given");
-  if (__builtin_mul_overflow(in.rows - 1, in.pitch, &span) ||
-      __builtin_add_overflow(span, run_b, &span) ||
-      __builtin_add_overflow(in.a, span, &end))
-    throw std::invalid_argument(who + ": source range overflows");
-  if (in.rows > 1 && (in.pitch < run_b || in.pitch % ss))
-    throw std::invalid_argument(who + ": rows overlap or pitch misaligned");
-  if (kind == BLOCK_LOAD) {
-    if (end > cap) throw std::invalid_argument(who + ": arena range out of bounds");
-    if (in.b == 0 || in.b % hs || __builtin_add_overflow(in.b, hp_b, &end))
-      throw std::invalid_argument(who + ": dst_ptr null, misaligned or overflowing");
-  } else {
-    if (in.a == 0 || in.a % ss)
-      throw std::invalid_argument(who + ": src_ptr null or misaligned");
-    if (kind == BLOCK_STORE &&
-        (__builtin_add_overflow(in.b, total, &end) || end > cap))
-      throw std::invalid_argument(who + ": arena range out of bounds");
-  }
-  return g;
-}
-
-static BlockArgs block_args(const BlockSegTuple& t) {
-  return {std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t),
-          std::get<4>(t), std::get<5>(t), std::get<6>(t), std::get<7>(t),
-          std::get<8>(t), std::get<9>(t), std::get<10>(t), std::get<11>(t),
-          std::get<12>(t), std::get<13>(t)};
-}
-
-static void block_check_ranges(int device, const std::string& who,
-                               BlockKind kind, const BlockSeg& g,
-                               std::vector<std::pair<uint64_t, uint64_t>>& known) {
-  uint64_t hs = cast_itemsize(g.dt);
-  if (kind == BLOCK_LOAD)
-    check_device_range(device, g.dst, g.dst + g.rows * g.run * hs, who,
-                       "dst_ptr", "destination", known);
-  else
-    check_device_range(device, g.src,
-                       g.src + (g.rows - 1) * g.src_pitch + g.run * hs, who,
-                       "src_ptr", "source", known);
-  auto range = block_scale_range(g);
-  check_device_range(device, g.scale_ptr + range.first * 4,
-                     g.scale_ptr + (range.second + 1) * 4, who, "scale_ptr",
-                     "scales", known);
-}
-
-static Tiles block_tiles(const std::vector<BlockSeg>& segs, const char* who) {
-  return build_tiles(
-      segs.size(), [&](size_t i) { return segs[i].rows * segs[i].run; },
-      [](size_t) { return (uint64_t)CAST_TILE; }, who);
-}
-
-// Segments: (src_ptr, dst_off, rows, run, src_pitch, src_dtype, dst_dtype,
-// scale_ptr, scale_e0, scale_pitch, M, K, bm, bn), F32/F16/BF16 -> F8_E4M3.
-static void arena_block_store_ptr(int h, std::vector<BlockSegTuple> segs_in) {
-  Arena* a = get_arena(h);
-  std::vector<BlockSeg> segs;
-  segs.reserve(segs_in.size());
-  for (auto& t : segs_in) {
-    BlockSeg g = block_validate("block store", BLOCK_STORE, a->cap,
-                                block_args(t));
-    if (g.rows * g.run) segs.push_back(g);
-  }
-  if (segs.empty()) return;
-  py::gil_scoped_release rel;
-  if (!a->is_dev()) {
-    for (auto& g : segs)
-      block_store_segment_host((const uint8_t*)g.src,
-                               (uint8_t*)a->base + g.dst, g);
-    return;
-  }
-  Tiles tiles = block_tiles(segs, "block store");
-  std::lock_guard<std::mutex> g(a->mu);
-  HIP_CHECK(hipSetDevice(a->device));
-  std::vector<std::pair<uint64_t, uint64_t>> known;
-  for (auto& s : segs)
-    block_check_ranges(a->device, "block store", BLOCK_STORE, s, known);
-  Scratch sc(a, tiles.room<BlockSeg>(segs.size()));
-  DevTiles<BlockSeg> d = upload_tiles(a, sc, segs, tiles);
-  launch(block_store_kernel, d.grid(), WG, a->kstream, (uint8_t*)a->base,
-         d.items, d.tile_item, d.tile_off, d.n_tiles);
-  // the sources are the caller's to free or overwrite once this returns
-  HIP_CHECK(hipStreamSynchronize(a->kstream));
-}
-
-// Segments: (src_off, dst_ptr, rows, run, src_pitch, src_dtype, dst_dtype,
-// scale_ptr, scale_e0, scale_pitch, M, K, bm, bn), F8_E4M3 -> F32/F16/BF16.
-static void arena_block_convert_ptr(int h, std::vector<BlockSegTuple> segs_in) {
-  Arena* a = get_arena(h);
-  std::vector<BlockSeg> segs;
-  segs.reserve(segs_in.size());
-  for (auto& t : segs_in) {
-    BlockArgs in = block_args(t);
-    std::swap(in.hp_dt, in.stored_dt);     // the tuple is (src, dst) ordered
-    BlockSeg g = block_validate("block convert", BLOCK_LOAD, a->cap, in);
-    if (g.rows * g.run) segs.push_back(g);
-  }
-  if (segs.empty()) return;
-  py::gil_scoped_release rel;
-  if (!a->is_dev()) {
-    for (auto& g : segs)
-      block_load_segment_host((const uint8_t*)a->base + g.src,
-                              (uint8_t*)g.dst, g);
-    return;
-  }
-  Tiles tiles = block_tiles(segs, "block convert");
-  std::lock_guard<std::mutex> g(a->mu);
-  HIP_CHECK(hipSetDevice(a->device));
-  std::vector<std::pair<uint64_t, uint64_t>> known;
-  for (auto& s : segs)
-    block_check_ranges(a->device, "block convert", BLOCK_LOAD, s, known);
-  Scratch sc(a, tiles.room<BlockSeg>(segs.size()));
-  DevTiles<BlockSeg> d = upload_tiles(a, sc, segs, tiles);
-  launch(block_load_kernel, d.grid(), WG, a->kstream, (const uint8_t*)a->base,
-         d.items, d.tile_item, d.tile_off, d.n_tiles);
-  HIP_CHECK(hipStreamSynchronize(a->kstream));
-}
-
-// Segments: (src_ptr, rows, run, src_pitch, src_dtype, out_ptr, scale_e0,
-// scale_pitch, M, K, bm, bn, n_slots): out_ptr[0:n_slots] are the f32 tile
-// scales of the segment's tensor; they are zeroed, receive each tile's amax
-// and become max(amax, 2^-40) / 448, as in absmax_scales.  Segments may
-// share slots.  device >= 0: block_absmax_kernel between two
-// scale_slots_kernel launches on the caller's thread stream; -1: the host
-// loops.
-typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                   uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
-                   uint64_t> BlockAbsmaxTuple;
-
-static void block_absmax_scales(int device,
-                                std::vector<BlockAbsmaxTuple> segs_in) {
-  if (device < -1) throw std::invalid_argument("block absmax: bad device");
-  std::vector<BlockSeg> segs;
-  std::vector<ScaleSlots> slots;
-  segs.reserve(segs_in.size());
-  for (auto& t : segs_in) {
-    BlockArgs in{std::get<0>(t), 0, std::get<1>(t), std::get<2>(t),
-                 std::get<3>(t), std::get<4>(t), DT_F8_E4M3, std::get<5>(t),
-                 std::get<6>(t), std::get<7>(t), std::get<8>(t),
-                 std::get<9>(t), std::get<10>(t), std::get<11>(t)};
-    uint64_t n_slots = std::get<12>(t), out_b, end;
-    if (n_slots == 0 || in.scale_ptr == 0 || in.scale_ptr % 4 ||
-        __builtin_mul_overflow(n_slots, (uint64_t)4, &out_b) ||
-        __builtin_add_overflow(in.scale_ptr, out_b, &end))
-      throw std::invalid_argument(
-          "block absmax: out_ptr null, misaligned, empty or overflowing");
-    BlockSeg g = block_validate("block absmax", BLOCK_ABSMAX, 0, in, n_slots);
-    if (g.rows * g.run) segs.push_back(g);
-    slots.push_back({in.scale_ptr, n_slots});
-  }
-  if (slots.empty()) return;
-  std::vector<ScaleSlots> merged = merge_scale_slots(std::move(slots));
-  py::gil_scoped_release rel;
-  if (device < 0) {
-    for (auto& r : merged) scale_slots_host(r, false);
-    for (auto& g : segs) block_absmax_segment_host(g);
-    for (auto& r : merged) scale_slots_host(r, true);
-    return;
-  }
-  Tiles tiles = block_tiles(segs, "block absmax");
-  HIP_CHECK(hipSetDevice(device));
-  std::vector<std::pair<uint64_t, uint64_t>> known;
-  for (auto& s : segs)
-    block_check_ranges(device, "block absmax", BLOCK_ABSMAX, s, known);
-  for (auto& r : merged)
-    check_device_range(device, r.ptr, r.ptr + r.n * 4, "block absmax",
-                       "out_ptr", "scales", known);
-  hipStream_t s = thread_stream(device);
-  size_t room = tiles.room<BlockSeg>(segs.size()) +
-                Scratch::room<ScaleSlots>(merged.size());
-  DevFree mem;
-  HIP_CHECK(hipMalloc(&mem.p, room));
-  Scratch sc(mem.p, room);
-  ScaleSlots* d_slots = sc.take<ScaleSlots>(merged.size());
-  HIP_CHECK(hipMemcpyAsync(d_slots, merged.data(),
-                           merged.size() * sizeof(ScaleSlots),
-                           hipMemcpyHostToDevice, s));
-  unsigned slot_grid = (unsigned)std::min<size_t>(merged.size(), 8192);
-  launch(scale_slots_kernel, slot_grid, WG, s, (const ScaleSlots*)d_slots,
-         (uint32_t)merged.size(), 0);
-  if (!tiles.empty()) {
-    DevTiles<BlockSeg> d = upload_tiles(s, sc, segs, tiles);
-    launch(block_absmax_kernel, d.grid(), WG, s, d.items, d.tile_item,
-           d.tile_off, d.n_tiles);
-  }
-  launch(scale_slots_kernel, slot_grid, WG, s, (const ScaleSlots*)d_slots,
-         (uint32_t)merged.size(), 1);
-  // the scales are read and the tables freed once this returns
-  HIP_CHECK(hipStreamSynchronize(s));
-}
-
-// host conversion of `n` packed elements, element i being element
-// scale_e0 + i of a tensor (..., M, K) under bm x bn tile scales:
-// quantising when dst_dtype is F8_E4M3, dequantising when src_dtype is (the
-// byte paths).  `scales` holds the tensor's f32 scales from index scale_g0
-// on; it must cover every tile the elements meet.
-static py::bytes block_convert_host(py::buffer src, uint64_t sdt, uint64_t ddt,
-                                    uint64_t n, py::buffer scales,
-                                    uint64_t scale_e0, uint64_t M, uint64_t K,
-                                    uint64_t bm, uint64_t bn,
-                                    uint64_t scale_g0) {
-  py::buffer_info bi = src.request(), sbi = scales.request();
-  bool quant = sdt <= DT_BF16;
-  BlockArgs in{0, 0, 1, n, 0, quant ? sdt : ddt, quant ? ddt : sdt,
-               (uint64_t)(uintptr_t)sbi.ptr, scale_e0, n, M, K, bm, bn};
-  uint64_t have = (uint64_t)bi.size * bi.itemsize;
-  BlockSeg g;
-  if (quant) {
-    in.a = (uint64_t)(uintptr_t)bi.ptr;
-    g = block_validate("block convert", BLOCK_STORE, ~0ull, in);
-    if (n > have / cast_itemsize(g.dt))
-      throw std::invalid_argument("block convert: source shorter than n");
-  } else {
-    // a load from a one-row "arena" that is the source buffer; the
-    // destination is this call's own
-    in.b = 8;
-    g = block_validate("block convert", BLOCK_LOAD, have, in);
-  }
-  if (n) {
-    auto range = block_scale_range(g);
-    uint64_t got = (uint64_t)sbi.size * sbi.itemsize / 4;
-    if (range.first < scale_g0 || range.second - scale_g0 >= got)
-      throw std::invalid_argument("block convert: scales do not cover the tiles");
-    g.scale_ptr -= 4 * scale_g0;           // index 0 of the tensor's scales
-  }
-  uint64_t out_b = quant ? n : n * cast_itemsize(g.dt);
-  if (out_b > (1ull << 40))
-    throw std::invalid_argument("block convert: segment size overflows");
-  std::vector<uint64_t> out(out_b / 8 + 1);
-  if (n) {
-    if (quant)
-      block_store_segment_host((const uint8_t*)bi.ptr, (uint8_t*)out.data(), g);
-    else
-      block_load_segment_host((const uint8_t*)bi.ptr, (uint8_t*)out.data(), g);
-  }
-  return py::bytes((const char*)out.data(), out_b);
 }
 
 static uintptr_t arena_base_ptr(int h) {

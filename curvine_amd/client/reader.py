@@ -38,6 +38,46 @@ class ReadDetector:
 
 
 
+def _slow_scales(scale, n):
+    """The scales a slow extent of `n` elements needs, by the scale fields
+    of its resolve_convert entry: (ctypes element type, first index, count,
+    convert).  scale_ptr[first : first + count] is fetched into a ctypes
+    array and convert(raw, src_code, dst_code, array) is the host converter
+    with its scale arguments rebased onto that array."""
+    import ctypes
+
+    from curvine_amd import native
+    if not scale:
+        return ctypes.c_float, 0, 0, \
+            lambda raw, sc, dc, _sbuf: native.convert_host(raw, sc, dc, n)
+    if len(scale) == 4:
+        # the E8M0 bytes of the blocks this extent touches
+        _sptr, e0, _spitch, blk = scale
+        g0, g1 = e0 // blk, (e0 + n - 1) // blk
+        return ctypes.c_uint8, g0, g1 - g0 + 1, \
+            lambda raw, sc, dc, sbuf: native.mx_convert_host(
+                raw, sc, dc, n, sbuf, e0 - g0 * blk)
+    if len(scale) == 7:
+        # the tile scales of the tensor rows this extent touches
+        _sptr, e0, _spitch, m, k, bm, bn = scale
+        tm, tn = -(-m // bm), -(-k // bn)
+
+        def tile_row(row):
+            return (row // m * tm + row % m // bm) * tn
+        g0 = tile_row(e0 // k)
+        return ctypes.c_float, g0, tile_row((e0 + n - 1) // k) + tn - g0, \
+            lambda raw, sc, dc, sbuf: native.block_convert_host(
+                raw, sc, dc, n, sbuf, e0, m, k, bm, bn, g0)
+    # the groups this extent touches
+    _sptr, every, e0 = scale
+    g0 = e0 // every if every else 0
+    g1 = (e0 + n - 1) // every if every else 0
+    return ctypes.c_float, g0, g1 - g0 + 1, \
+        lambda raw, sc, dc, sbuf: native.convert_host(
+            raw, sc, dc, n, scales=sbuf, scale_every=every,
+            scale_e0=e0 - g0 * every)
+
+
 def _hole_span(offs, blocks, length, pos) -> int:
     """Length of the zero hole at file offset pos, or 0 when pos falls
     inside a cached block extent.  Metadata length may exceed block
@@ -401,78 +441,30 @@ class SyncLocalReader:
     def exec_convert(self, groups, slow, dst_on_device: bool) -> None:
         """Run a resolve_convert plan: one Arena.convert_ptr per arena,
         then the slow list through pread -> host convert (the kernel's own
-        scalar routines) -> H2D copy or memcpy."""
+        scalar routines) -> H2D copy or memcpy, the scales an extent needs
+        fetched to the host first."""
         import ctypes
 
         from curvine_amd import native
         for arena, segs in groups:
             arena.convert_ptr(segs)
         for off, n, sdt, ddt, dptr, *scale in slow:
+            sc, dc = native.DTYPES[sdt], native.DTYPES[ddt]
+            ctype, first, count, convert = _slow_scales(scale, n)
+            sbuf = (ctype * count)()
+            if count:
+                src = scale[0] + first * ctypes.sizeof(ctype)
+                if dst_on_device:
+                    native.load().memcpy_d2h(ctypes.addressof(sbuf), src,
+                                             ctypes.sizeof(sbuf))
+                else:
+                    ctypes.memmove(sbuf, src, ctypes.sizeof(sbuf))
             nbytes = n * native.DTYPE_BITS[sdt] // 8
-            if len(scale) == 4:
-                # the E8M0 bytes of the blocks this extent touches
-                sptr, e0, _spitch, blk = scale
-                g0, g1 = e0 // blk, (e0 + n - 1) // blk
-                sbuf = (ctypes.c_uint8 * (g1 - g0 + 1))()
-                if dst_on_device:
-                    native.load().memcpy_d2h(ctypes.addressof(sbuf),
-                                             sptr + g0, len(sbuf))
-                else:
-                    ctypes.memmove(sbuf, sptr + g0, len(sbuf))
-                raw = self.pread(off, nbytes)
-                if len(raw) != nbytes:
-                    raise err.OutOfRange(
-                        f"typed read at {off}: short read ({len(raw)} bytes)")
-                out = native.mx_convert_host(
-                    raw, native.DTYPES[sdt], native.DTYPES[ddt], n, sbuf,
-                    e0 - g0 * blk)
-                self._land(out, dptr, dst_on_device)
-                continue
-            if len(scale) == 7:
-                # the tile scales of the tensor rows this extent touches
-                sptr, e0, _spitch, m, k, bm, bn = scale
-                tm, tn = -(-m // bm), -(-k // bn)
-
-                def tile_row(row):
-                    return (row // m * tm + row % m // bm) * tn
-                g0 = tile_row(e0 // k)
-                g1 = tile_row((e0 + n - 1) // k) + tn
-                sbuf = (ctypes.c_float * (g1 - g0))()
-                if dst_on_device:
-                    native.load().memcpy_d2h(ctypes.addressof(sbuf),
-                                             sptr + 4 * g0, 4 * len(sbuf))
-                else:
-                    ctypes.memmove(sbuf, sptr + 4 * g0, 4 * len(sbuf))
-                raw = self.pread(off, nbytes)
-                if len(raw) != nbytes:
-                    raise err.OutOfRange(
-                        f"typed read at {off}: short read ({len(raw)} bytes)")
-                out = native.block_convert_host(
-                    raw, native.DTYPES[sdt], native.DTYPES[ddt], n, sbuf,
-                    e0, m, k, bm, bn, g0)
-                self._land(out, dptr, dst_on_device)
-                continue
-            kw = {}
-            if scale:
-                # the groups this extent touches, fetched to the host
-                sptr, every, e0 = scale
-                g0 = e0 // every if every else 0
-                g1 = (e0 + n - 1) // every if every else 0
-                sbuf = (ctypes.c_float * (g1 - g0 + 1))()
-                if dst_on_device:
-                    native.load().memcpy_d2h(ctypes.addressof(sbuf),
-                                             sptr + 4 * g0, 4 * len(sbuf))
-                else:
-                    ctypes.memmove(sbuf, sptr + 4 * g0, 4 * len(sbuf))
-                kw = {"scales": sbuf, "scale_every": every,
-                      "scale_e0": e0 - g0 * every}
             raw = self.pread(off, nbytes)
             if len(raw) != nbytes:
                 raise err.OutOfRange(
                     f"typed read at {off}: short read ({len(raw)} bytes)")
-            out = native.convert_host(raw, native.DTYPES[sdt],
-                                      native.DTYPES[ddt], n, **kw)
-            self._land(out, dptr, dst_on_device)
+            self._land(convert(raw, sc, dc, sbuf), dptr, dst_on_device)
 
     # ---------------- token windows ----------------
     def resolve_token_windows(self, windows, src_dtype: str, seq_len: int,

@@ -26,10 +26,10 @@ _mod = None
 
 def build_native(force: bool = False) -> str:
     """Compile csrc/ into curvine_amd/_native.so for gfx950.  The .so is
-    stale when any csrc/*.cpp or csrc/*.hip is newer than it."""
+    stale when any csrc/*.cpp, *.hip or *.h is newer than it."""
     if not force and os.path.exists(_SO) and os.path.exists(_SRC):
         sources = [os.path.join(_CSRC, f) for f in os.listdir(_CSRC)
-                   if f.endswith((".cpp", ".hip"))]
+                   if f.endswith((".cpp", ".hip", ".h"))]
         if os.path.getmtime(_SO) >= max(map(os.path.getmtime, sources)):
             return _SO
     import pybind11

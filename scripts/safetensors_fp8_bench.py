@@ -34,6 +34,7 @@ CASES = ("save_big", "save_many", "load_big", "load_many")
 def stats(samples_s):
     us = [s * 1e6 for s in samples_s]
     return {"median_us": round(statistics.median(us), 1),
+            "mean_us": round(statistics.fmean(us), 1),
             "min_us": round(min(us), 1), "max_us": round(max(us), 1),
             "stdev_us": round(statistics.stdev(us), 1) if len(us) > 1 else 0.0,
             "repeats": len(us)}

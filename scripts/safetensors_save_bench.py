@@ -35,6 +35,7 @@ NAME = {torch.float32: "F32", torch.bfloat16: "BF16"}
 def stats(samples_s, calls=1):
     us = [s / calls * 1e6 for s in samples_s]
     return {"median_us": round(statistics.median(us), 1),
+            "mean_us": round(statistics.fmean(us), 1),
             "min_us": round(min(us), 1), "max_us": round(max(us), 1),
             "stdev_us": round(statistics.stdev(us), 1) if len(us) > 1 else 0.0,
             "repeats": len(us)}
