@@ -155,6 +155,7 @@ static uint32_t crc32c_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
 #include "block_cast.hip"
 #include "token_gather.hip"
 #include "token_docs.hip"
+#include "token_pack.hip"
 
 // ---------------------------------------------------------------------------
 // GPU availability
@@ -1298,6 +1299,392 @@ static std::pair<uint64_t, uint64_t> token_docs(
   return {result[0], result[1]};
 }
 
+// ---- document-packed token batches (token_pack.hip) ----
+
+// a host arena works with the CPU: device memory is the wrong side
+static void token_check_host_side(std::initializer_list<uintptr_t> ptrs,
+                                  const char* msg) {
+  for (uintptr_t p : ptrs) {
+    hipPointerAttribute_t at;
+    if (!p) continue;
+    if (hipPointerGetAttributes(&at, (const void*)p) != hipSuccess) {
+      (void)hipGetLastError();   // plain host memory, or no runtime
+      continue;
+    }
+    if (at.type == hipMemoryTypeDevice) throw std::invalid_argument(msg);
+  }
+}
+
+// eos_id as the widened value a token is compared with
+static uint64_t token_eos_value(int64_t eos_id, uint64_t sdt, const char* who) {
+  int64_t top = sdt == DT_U16 ? 0xFFFF
+                : sdt == DT_U32 ? (int64_t)0xFFFFFFFFll : (int64_t)INT32_MAX;
+  if (eos_id < 0 || eos_id > top)
+    throw std::invalid_argument(std::string(who) +
+                                ": eos_id negative or outside the dtype");
+  return (uint64_t)eos_id;
+}
+
+// Spans: (src_off, tok0, n): n src_dtype tokens at arena byte src_off are
+// tokens tok0 .. tok0+n-1 of a file, in ascending tok0 without overlap.  The
+// file indices of the tokens equal to eos_id go to out_ptr (int64, room for
+// `capacity`), ascending; hits past `capacity` are counted, not written.
+// Returns the number of hits.  capacity 0 is a pure count (out_ptr may be 0).
+// Device arena: count, offsets and (capacity > 0) write kernels on kstream
+// and one D2H copy of the total; host arena: the host loop.  Every argument
+// error is raised here, on the host, before anything runs.
+typedef std::tuple<uint64_t, uint64_t, uint64_t> TokenSpanTuple;
+
+static uint64_t arena_token_eos_index(int h, std::vector<TokenSpanTuple> spans_in,
+                                      uint64_t sdt, int64_t eos_id,
+                                      uintptr_t out_ptr, uint64_t capacity) {
+  const char* who = "token eos index";
+  Arena* a = get_arena(h);
+  if (sdt >= DT_COUNT)
+    throw std::invalid_argument("token eos index: unknown dtype code");
+  if (!token_pair_supported((uint32_t)sdt, DT_I64))
+    throw std::invalid_argument("token eos index: unsupported dtype");
+  uint64_t eos = token_eos_value(eos_id, sdt, who);
+  uint64_t ss = cast_itemsize((uint32_t)sdt), out_b, out_end;
+  if (__builtin_mul_overflow(capacity, (uint64_t)8, &out_b) ||
+      __builtin_add_overflow((uint64_t)out_ptr, out_b, &out_end))
+    throw std::invalid_argument("token eos index: size overflows");
+  if ((capacity && out_ptr == 0) || out_ptr % 8)
+    throw std::invalid_argument("token eos index: out_ptr null or misaligned");
+  std::vector<TokenSpan> spans;
+  spans.reserve(spans_in.size());
+  uint64_t next_tok = 0;
+  for (auto& t : spans_in) {
+    TokenSpan g{std::get<0>(t), std::get<1>(t), std::get<2>(t)};
+    uint64_t last, src_b, end;
+    if (g.n == 0)
+      throw std::invalid_argument("token eos index: span without tokens");
+    if (__builtin_add_overflow(g.tok0, g.n, &last) || last > (1ull << 62) ||
+        __builtin_mul_overflow(g.n, ss, &src_b) ||
+        __builtin_add_overflow(g.src_off, src_b, &end))
+      throw std::invalid_argument("token eos index: size overflows");
+    if (g.tok0 < next_tok)
+      throw std::invalid_argument(
+          "token eos index: spans not ascending, or overlapping");
+    if (end > a->cap)
+      throw std::invalid_argument("token eos index: arena range out of bounds");
+    next_tok = last;
+    spans.push_back(g);
+  }
+  py::gil_scoped_release rel;
+  int64_t* out = (int64_t*)out_ptr;
+  if (!a->is_dev()) {
+    token_check_host_side({out_ptr},
+                          "token eos index: device destination on a host arena");
+    uint64_t total = 0;
+    for (auto& g : spans)
+      total = token_eos_host((const uint8_t*)a->base, g, (uint32_t)sdt, eos,
+                             out, capacity, total);
+    return total;
+  }
+  Tiles tiles = build_tiles(
+      spans.size(), [&](size_t i) { return spans[i].n; },
+      [](size_t) { return (uint64_t)TOKEN_EOS_TILE; }, who);
+  std::lock_guard<std::mutex> g(a->mu);
+  HIP_CHECK(hipSetDevice(a->device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  if (capacity)
+    check_device_range(a->device, out_ptr, out_end, who, "out_ptr",
+                       "destination", known);
+  if (tiles.empty()) return 0;   // nothing to scan: no grid-0 launch
+  size_t n_tiles = tiles.item.size();
+  Scratch sc(a, Scratch::room<unsigned long long>(1) +
+                    Scratch::room<uint64_t>(n_tiles) +
+                    tiles.room<TokenSpan>(spans.size()));
+  unsigned long long* d_total = sc.take<unsigned long long>(1);
+  uint64_t* d_counts = sc.take<uint64_t>(n_tiles);
+  DevTiles<TokenSpan> d = upload_tiles(a, sc, spans, tiles);
+  const uint8_t* base = (const uint8_t*)a->base;
+  launch(token_eos_count_kernel, d.grid(), WG, a->kstream, base, d.items,
+         d.tile_item, d.tile_off, d.n_tiles, (uint32_t)sdt, eos, d_counts);
+  launch(token_eos_offsets_kernel, 1u, WG, a->kstream, d_counts,
+         (uint64_t)n_tiles, d_total);
+  if (capacity)
+    launch(token_eos_write_kernel, d.grid(), WG, a->kstream, base, d.items,
+           d.tile_item, d.tile_off, d.n_tiles, (uint32_t)sdt, eos,
+           (const uint64_t*)d_counts, out, capacity);
+  unsigned long long total = 0;
+  HIP_CHECK(hipMemcpyAsync(&total, d_total, sizeof(total),
+                           hipMemcpyDeviceToHost, a->kstream));
+  HIP_CHECK(hipStreamSynchronize(a->kstream));
+  return total;
+}
+
+// host scan of `n` packed tokens, tokens tok0 .. tok0+n-1 of a file (the
+// slow path of the reader's eos index): the hits' file indices as int64
+static py::bytes token_eos_index_host(py::buffer src, uint64_t sdt,
+                                      int64_t eos_id, uint64_t tok0,
+                                      uint64_t n) {
+  py::buffer_info bi = src.request();
+  if (sdt >= DT_COUNT)
+    throw std::invalid_argument("token eos index: unknown dtype code");
+  if (!token_pair_supported((uint32_t)sdt, DT_I64))
+    throw std::invalid_argument("token eos index: unsupported dtype");
+  uint64_t eos = token_eos_value(eos_id, sdt, "token eos index");
+  uint64_t ss = cast_itemsize((uint32_t)sdt), src_b, last;
+  if (__builtin_mul_overflow(n, ss, &src_b) ||
+      __builtin_add_overflow(tok0, n, &last) || last > (1ull << 62))
+    throw std::invalid_argument("token eos index: size overflows");
+  if (src_b > (uint64_t)bi.size * bi.itemsize)
+    throw std::invalid_argument(
+        "token eos index: source shorter than n tokens");
+  TokenSpan g{0, tok0, n};
+  const uint8_t* s = (const uint8_t*)bi.ptr;
+  uint64_t total = token_eos_host(s, g, (uint32_t)sdt, eos, nullptr, 0, 0);
+  std::vector<int64_t> out(total + 1);
+  token_eos_host(s, g, (uint32_t)sdt, eos, out.data(), total, 0);
+  return py::bytes((const char*)out.data(), total * 8);
+}
+
+// sentinels of a packed batch have to be values of the destination dtype
+static void token_check_fits(int64_t v, uint64_t ddt, const char* what) {
+  if (ddt == DT_I32 && (v < (int64_t)INT32_MIN || v > (int64_t)INT32_MAX))
+    throw std::invalid_argument(std::string("token pack: ") + what +
+                                " does not fit the dtype");
+}
+
+// One segment (row, col, n, pos0, doc, seq, flags) and the checks every
+// caller shares; flags: TOKEN_SEG_NEXT, or TOKEN_SEG_PAD alone
+typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t, uint64_t, uint64_t,
+                   uint64_t> TokenSegTuple;
+
+static TokenSeg token_seg_checked(const TokenSegTuple& t, uint64_t rows,
+                                  uint64_t seq_len, uint64_t n_segs,
+                                  uint64_t ddt) {
+  TokenSeg s{std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t),
+             (int64_t)std::get<4>(t), (uint32_t)std::get<5>(t),
+             (uint32_t)std::get<6>(t)};
+  uint64_t last, pos_top;
+  uint64_t top = ddt == DT_I32 ? (uint64_t)INT32_MAX : (uint64_t)INT64_MAX;
+  if (s.n == 0)
+    throw std::invalid_argument("token pack: segment without columns");
+  if (s.row >= rows)
+    throw std::invalid_argument("token pack: segment row outside the batch");
+  if (__builtin_add_overflow(s.col, s.n, &last) || last > seq_len)
+    throw std::invalid_argument("token pack: segment runs past its row");
+  if (std::get<5>(t) >= n_segs)
+    throw std::invalid_argument("token pack: seq outside the segment list");
+  if (std::get<6>(t) > TOKEN_SEG_PAD)
+    throw std::invalid_argument("token pack: unknown segment flags");
+  if (__builtin_add_overflow(s.pos0, s.n, &pos_top) || pos_top - 1 > top ||
+      std::get<4>(t) > top)
+    throw std::invalid_argument(
+        "token pack: position or document id overflows the dtype");
+  return s;
+}
+
+// Segments: (row, col, n, pos0, doc, seq, flags); pieces: (src_off, segment,
+// j0, k): k source tokens at arena byte src_off are tokens j0 .. j0+k-1 of
+// source segment `segment` (see token_pack.hip).  x, y, position_ids and
+// doc_ids are dense [rows, seq_len] arrays of dst_dtype, cu_seqlens int32
+// with n_segments + 1 entries; every pointer but x_ptr may be 0, which skips
+// that output.  Pad segments are filled and cu_seqlens written whatever the
+// pieces cover.  Returns the tokens read that lie outside [0, vocab_size) (0
+// when vocab_size is 0).  Device arena: the tables are uploaded and
+// token_pack_kernel launched once on kstream; host arena: the host loop.
+// Every argument error is raised here, on the host, before anything runs.
+static uint64_t arena_token_pack(int h, std::vector<TokenSegTuple> segs_in,
+                                 std::vector<TokenPieceTuple> pieces_in,
+                                 uintptr_t x_ptr, uintptr_t y_ptr,
+                                 uintptr_t pos_ptr, uintptr_t doc_ptr,
+                                 uintptr_t cu_ptr, uint64_t rows,
+                                 uint64_t seq_len, uint64_t sdt, uint64_t ddt,
+                                 int64_t pad_id, int64_t ignore_index,
+                                 uint64_t vocab) {
+  const char* who = "token pack";
+  Arena* a = get_arena(h);
+  if (sdt >= DT_COUNT || ddt >= DT_COUNT)
+    throw std::invalid_argument("token pack: unknown dtype code");
+  if (!token_pair_supported((uint32_t)sdt, (uint32_t)ddt))
+    throw std::invalid_argument("token pack: unsupported dtype pair");
+  if (rows == 0 || seq_len == 0)
+    throw std::invalid_argument("token pack: rows and seq_len must be positive");
+  uint64_t ss = cast_itemsize((uint32_t)sdt), ds = cast_itemsize((uint32_t)ddt);
+  uint64_t n_segs = segs_in.size();
+  uint64_t n_el, dst_b, x_end, y_end, pos_end, doc_end, cu_end;
+  if (n_segs >= 0xFFFFFFFFull || pieces_in.size() >= 0xFFFFFFFFull ||
+      __builtin_mul_overflow(rows, seq_len, &n_el) ||
+      __builtin_mul_overflow(n_el, ds, &dst_b) ||
+      __builtin_add_overflow((uint64_t)x_ptr, dst_b, &x_end) ||
+      __builtin_add_overflow((uint64_t)y_ptr, dst_b, &y_end) ||
+      __builtin_add_overflow((uint64_t)pos_ptr, dst_b, &pos_end) ||
+      __builtin_add_overflow((uint64_t)doc_ptr, dst_b, &doc_end) ||
+      __builtin_add_overflow((uint64_t)cu_ptr, (n_segs + 1) * 4, &cu_end))
+    throw std::invalid_argument("token pack: size overflows");
+  if (cu_ptr && n_el >= (1ull << 31))
+    throw std::invalid_argument(
+        "token pack: cu_seqlens needs rows * seq_len below 2^31");
+  if (x_ptr == 0 || x_ptr % ds)
+    throw std::invalid_argument("token pack: x_ptr null or misaligned");
+  if (y_ptr % ds) throw std::invalid_argument("token pack: y_ptr misaligned");
+  if (pos_ptr % ds)
+    throw std::invalid_argument("token pack: pos_ptr misaligned");
+  if (doc_ptr % ds)
+    throw std::invalid_argument("token pack: doc_ptr misaligned");
+  if (cu_ptr % 4) throw std::invalid_argument("token pack: cu_ptr misaligned");
+  token_check_fits(pad_id, ddt, "pad_id");
+  token_check_fits(ignore_index, ddt, "ignore_index");
+  std::vector<TokenSeg> segs;
+  segs.reserve(n_segs);
+  for (auto& t : segs_in)
+    segs.push_back(token_seg_checked(t, rows, seq_len, n_segs, ddt));
+  // the items of the launch: the source pieces, then the pad segments
+  std::vector<TokenPackPiece> items;
+  items.reserve(pieces_in.size());
+  for (auto& t : pieces_in) {
+    TokenPackPiece g{std::get<0>(t), std::get<1>(t), std::get<2>(t),
+                     std::get<3>(t)};
+    uint64_t last, src_b, end;
+    if (g.seg >= n_segs)
+      throw std::invalid_argument("token pack: piece of an unknown segment");
+    const TokenSeg& s = segs[g.seg];
+    if (s.flags & TOKEN_SEG_PAD)
+      throw std::invalid_argument("token pack: piece on a pad segment");
+    if (g.k == 0)
+      throw std::invalid_argument("token pack: piece without tokens");
+    if (__builtin_add_overflow(g.j0, g.k, &last) ||
+        __builtin_mul_overflow(g.k, ss, &src_b) ||
+        __builtin_add_overflow(g.src_off, src_b, &end))
+      throw std::invalid_argument("token pack: size overflows");
+    if (last > s.n + (s.flags & TOKEN_SEG_NEXT))
+      throw std::invalid_argument("token pack: piece runs past its segment");
+    if (end > a->cap)
+      throw std::invalid_argument("token pack: arena range out of bounds");
+    items.push_back(g);
+  }
+  for (size_t i = 0; i < segs.size(); ++i)
+    if (segs[i].flags & TOKEN_SEG_PAD)
+      items.push_back(TokenPackPiece{0, (uint64_t)i, 0, segs[i].n});
+  py::gil_scoped_release rel;
+  TokenPackOut out{(uint8_t*)x_ptr, (uint8_t*)y_ptr, (uint8_t*)pos_ptr,
+                   (uint8_t*)doc_ptr};
+  int32_t* cu = (int32_t*)cu_ptr;
+  if (!a->is_dev()) {
+    token_check_host_side({x_ptr, y_ptr, pos_ptr, doc_ptr, cu_ptr},
+                          "token pack: device destination on a host arena");
+    return token_pack_host((const uint8_t*)a->base, segs, items, out, cu, rows,
+                           seq_len, (uint32_t)sdt, (uint32_t)ddt, pad_id,
+                           ignore_index, vocab);
+  }
+  Tiles tiles = build_tiles(
+      items.size(), [&](size_t i) { return items[i].k; },
+      [](size_t) { return (uint64_t)TOKEN_PACK_TILE; }, who);
+  std::lock_guard<std::mutex> g(a->mu);
+  HIP_CHECK(hipSetDevice(a->device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  check_device_range(a->device, x_ptr, x_end, who, "x_ptr", "destination",
+                     known);
+  if (y_ptr)
+    check_device_range(a->device, y_ptr, y_end, who, "y_ptr", "destination",
+                       known);
+  if (pos_ptr)
+    check_device_range(a->device, pos_ptr, pos_end, who, "pos_ptr",
+                       "destination", known);
+  if (doc_ptr)
+    check_device_range(a->device, doc_ptr, doc_end, who, "doc_ptr",
+                       "destination", known);
+  if (cu_ptr)
+    check_device_range(a->device, cu_ptr, cu_end, who, "cu_ptr", "destination",
+                       known);
+  if (tiles.empty() && !cu) return 0;   // nothing to write: no launch
+  Scratch sc(a, Scratch::room<unsigned long long>(1) +
+                    Scratch::room<TokenSeg>(segs.size()) +
+                    tiles.room<TokenPackPiece>(items.size()));
+  unsigned long long* d_count = sc.take<unsigned long long>(1);
+  TokenSeg* d_segs = sc.take<TokenSeg>(segs.size());
+  if (vocab) HIP_CHECK(hipMemsetAsync(d_count, 0, sizeof(*d_count), a->kstream));
+  if (!segs.empty())
+    HIP_CHECK(hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(TokenSeg),
+                             hipMemcpyHostToDevice, a->kstream));
+  DevTiles<TokenPackPiece> d{nullptr, nullptr, nullptr, 0};
+  if (!tiles.empty()) d = upload_tiles(a, sc, items, tiles);
+  launch(token_pack_kernel, std::max(d.grid(), 1u), WG, a->kstream,
+         (const uint8_t*)a->base, (const TokenSeg*)d_segs, (uint32_t)n_segs,
+         d.items, d.tile_item, d.tile_off, d.n_tiles, out, cu, rows, seq_len,
+         (uint32_t)sdt, (uint32_t)ddt, pad_id, ignore_index, vocab, d_count);
+  unsigned long long bad = 0;
+  if (vocab)
+    HIP_CHECK(hipMemcpyAsync(&bad, d_count, sizeof(bad), hipMemcpyDeviceToHost,
+                             a->kstream));
+  // the tables are host vectors of this call: wait before they go
+  HIP_CHECK(hipStreamSynchronize(a->kstream));
+  return bad;
+}
+
+// One piece on the host (the slow path of the reader's packed batches: file
+// tier, cross-side arenas, holes and the token a block boundary cuts), with
+// the pack kernel's own scalar routines.  `src` holds tokens j0 .. j0+k-1 of
+// a source segment (n, pos0, doc, flags); a pad segment has no source and
+// is done whole (j0 = 0, k = n).  Returns (x, y, pos, doc, bad) as bytes of
+// dst_dtype: x / pos / doc for the segment's columns j0 .. min(j0+k, n)-1,
+// y for its columns max(j0, 1)-1 onwards (pad: all n), ignore_index at
+// column n-1 included when the document ends inside the piece.
+static py::tuple token_pack_piece_host(py::buffer src, uint64_t n,
+                                       uint64_t pos0, uint64_t doc,
+                                       uint64_t flags, uint64_t j0, uint64_t k,
+                                       uint64_t sdt, uint64_t ddt,
+                                       int64_t pad_id, int64_t ignore_index,
+                                       uint64_t vocab) {
+  py::buffer_info bi = src.request();
+  if (sdt >= DT_COUNT || ddt >= DT_COUNT)
+    throw std::invalid_argument("token pack: unknown dtype code");
+  if (!token_pair_supported((uint32_t)sdt, (uint32_t)ddt))
+    throw std::invalid_argument("token pack: unsupported dtype pair");
+  token_check_fits(pad_id, ddt, "pad_id");
+  token_check_fits(ignore_index, ddt, "ignore_index");
+  // the segment alone in a row of its own
+  TokenSeg s = token_seg_checked(
+      TokenSegTuple{0, 0, n, pos0, doc, 0, flags}, 1, n, 1, ddt);
+  bool is_pad = s.flags & TOKEN_SEG_PAD;
+  uint32_t ss = cast_itemsize((uint32_t)sdt), ds = cast_itemsize((uint32_t)ddt);
+  uint64_t last, src_b;
+  if (k == 0) throw std::invalid_argument("token pack: piece without tokens");
+  if (__builtin_add_overflow(j0, k, &last) ||
+      __builtin_mul_overflow(k, (uint64_t)ss, &src_b) || k > (1ull << 36))
+    throw std::invalid_argument("token pack: size overflows");
+  if (is_pad ? (j0 != 0 || k != n) : last > s.n + (s.flags & TOKEN_SEG_NEXT))
+    throw std::invalid_argument("token pack: piece runs past its segment");
+  if (!is_pad && src_b > (uint64_t)bi.size * bi.itemsize)
+    throw std::invalid_argument("token pack: source shorter than k tokens");
+  // the columns from c on as a segment of their own: token j becomes j - c,
+  // and a piece that begins past token 0 keeps j - c >= 1 (it still goes to
+  // y).  k + 1 elements of 8-byte words, aligned for both itemsizes.
+  uint64_t c = !is_pad && j0 >= 1 ? j0 - 1 : 0;
+  s.n -= c;
+  s.pos0 += c;
+  j0 -= c;
+  last -= c;
+  size_t words = (size_t)((k + 1) * ds / 8 + 1);
+  std::vector<uint64_t> bx(words), by(words), bp(words), bd(words);
+  TokenPackOut o{(uint8_t*)bx.data(), (uint8_t*)by.data(), (uint8_t*)bp.data(),
+                 (uint8_t*)bd.data()};
+  uint64_t bad = 0, x1 = std::min(last, s.n), y1 = last;
+  if (is_pad) {
+    for (uint64_t i = 0; i < k; ++i)
+      token_pack_pad_one(o, i, pad_id, ignore_index, ds);
+  } else {
+    const uint8_t* p = (const uint8_t*)bi.ptr;
+    for (uint64_t i = 0; i < k; ++i)
+      bad += token_pack_one(p + i * ss, o, s, j0 + i, (uint32_t)sdt, ss, ds,
+                            vocab);
+    y1 = last - 1;
+    if (!(s.flags & TOKEN_SEG_NEXT) && last == s.n) {
+      token_pack_end(o, s, ignore_index, ds);
+      y1 = s.n;
+    }
+  }
+  auto cut = [&](const uint8_t* b, uint64_t c0, uint64_t c1) {
+    return py::bytes((const char*)b + c0 * ds, c1 > c0 ? (c1 - c0) * ds : 0);
+  };
+  return py::make_tuple(cut(o.x, j0, x1), cut(o.y, 0, y1), cut(o.pos, j0, x1),
+                        cut(o.doc, j0, x1), bad);
+}
+
 static uintptr_t arena_base_ptr(int h) {
   return (uintptr_t)get_arena(h)->base;
 }
@@ -1980,6 +2367,10 @@ PYBIND11_MODULE(_native, m) {
   m.def("token_convert_host", &token_convert_host);
   m.def("absmax_scales", &absmax_scales);
   m.def("token_docs", &token_docs);
+  m.def("arena_token_eos_index", &arena_token_eos_index);
+  m.def("token_eos_index_host", &token_eos_index_host);
+  m.def("arena_token_pack", &arena_token_pack);
+  m.def("token_pack_piece_host", &token_pack_piece_host);
   m.def("arena_mx_store_ptr", &arena_mx_store_ptr);
   m.def("arena_mx_convert_ptr", &arena_mx_convert_ptr);
   m.def("mx_scales", &mx_scales);
@@ -2066,5 +2457,9 @@ PYBIND11_MODULE(_native, m) {
   m.attr("CAST_TILE") = CAST_TILE;
   m.attr("TOKEN_TILE") = TOKEN_TILE;
   m.attr("TOKEN_DOC_CHUNK") = TOKEN_DOC_CHUNK;
+  m.attr("TOKEN_EOS_TILE") = TOKEN_EOS_TILE;
+  m.attr("TOKEN_PACK_TILE") = TOKEN_PACK_TILE;
+  m.attr("TOKEN_SEG_NEXT") = TOKEN_SEG_NEXT;
+  m.attr("TOKEN_SEG_PAD") = TOKEN_SEG_PAD;
   m.attr("__hip_arch__") = "gfx950";
 }

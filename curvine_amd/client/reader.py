@@ -561,6 +561,199 @@ class SyncLocalReader:
                            if v < 0 or v >= vocab_size)
         return bad
 
+    # ---------------- document-packed token batches ----------------
+    def _token_parts(self, off: int, n_tok: int, ss: int,
+                     dst_on_device: bool):
+        """Cut n_tok tokens of ss bytes at file byte `off` on whole tokens
+        at block boundaries: yields (arena or None, src_off or file_off,
+        e, k) for tokens e .. e+k-1.  arena is None for what has to go
+        through pread: file tier, cross-side arenas, holes (which read as
+        zeros) and the single token that straddles two blocks."""
+        import bisect
+        blocks = self.fb.blocks
+        e = 0
+        while e < n_tok:
+            p = off + e * ss
+            hole = _hole_span(self._offs, blocks, self.length, p)
+            if hole > 0:
+                k = min(n_tok - e, -(-hole // ss))
+                yield None, p, e, k
+                e += k
+                continue
+            idx = bisect.bisect_right(self._offs, p) - 1
+            lb = blocks[idx]
+            k = min(n_tok - e, (lb.offset + lb.block.length - p) // ss)
+            if k == 0:                # token straddles two blocks
+                yield None, p, e, 1
+                e += 1
+                continue
+            r = self._readers[idx]
+            arena = getattr(r.layout, "arena", None)
+            same_side = r.meta.get("kind") == "arena" and \
+                arena is not None and \
+                ((arena.device >= 0) == bool(dst_on_device))
+            if same_side:
+                yield arena, r.meta["offset"] + p - lb.offset, e, k
+            else:
+                yield None, p, e, k
+            e += k
+
+    def token_eos_index(self, src_dtype: str, header_bytes: int, eos_id: int,
+                        dst_on_device: bool):
+        """The document index of a token file: the ascending array('q') of
+        the token indices (token t sits at byte header_bytes + t *
+        itemsize) whose value is eos_id.  Spans inside arena blocks on the
+        side `dst_on_device` names go through Arena.token_eos_index, one
+        count call and one write call per arena and one copy back;
+        everything else (file tier, cross-side arenas, holes, a token that
+        straddles two blocks) through pread and native.token_eos_index_host
+        in bounded chunks.  A trailing partial token is ignored."""
+        import array
+        import ctypes
+
+        from curvine_amd import native
+        sc = native.DTYPES[src_dtype]
+        ss = native.DTYPE_ITEMSIZE[src_dtype]
+        if header_bytes < 0:
+            raise err.InvalidArgument("token eos index: negative header_bytes")
+        n_tok = max(0, self.length - header_bytes) // ss
+        groups: dict[int, tuple[object, list]] = {}
+        runs = []                     # ascending arrays, one per source
+        slow = array.array("q")
+        step = (4 << 20) // ss        # tokens per pread
+        for arena, at, e, k in self._token_parts(header_bytes, n_tok, ss,
+                                                 dst_on_device):
+            if arena is not None:
+                groups.setdefault(arena.handle, (arena, []))[1].append(
+                    (at, e, k))
+                continue
+            for c in range(0, k, step):
+                kk = min(step, k - c)
+                raw = self.pread(at + c * ss, kk * ss)
+                if len(raw) != kk * ss:
+                    raise err.OutOfRange(
+                        f"token read at {at + c * ss}: short read "
+                        f"({len(raw)} bytes)")
+                slow.frombytes(native.token_eos_index_host(
+                    raw, sc, eos_id, e + c, kk))
+        if len(slow):
+            runs.append(slow)
+        for arena, spans in groups.values():
+            total = arena.token_eos_index(spans, sc, eos_id, 0, 0)
+            if not total:
+                continue
+            got = array.array("q")
+            if arena.device >= 0:
+                import torch
+                t = torch.empty(total, dtype=torch.int64,
+                                device=f"cuda:{arena.device}")
+                arena.token_eos_index(spans, sc, eos_id, t.data_ptr(), total)
+                got.frombytes(t.cpu().numpy().tobytes())
+            else:
+                buf = (ctypes.c_int64 * total)()
+                arena.token_eos_index(spans, sc, eos_id,
+                                      ctypes.addressof(buf), total)
+                got.frombytes(bytes(buf))
+            runs.append(got)
+        if len(runs) == 1:
+            return runs[0]
+        merged = array.array("q")
+        for r in runs:
+            merged.extend(r)
+        return array.array("q", sorted(merged))   # ascending runs: one merge
+
+    def resolve_token_pack(self, items, src_dtype: str, dst_on_device: bool):
+        """Resolution half of a packed batch, modelled on
+        resolve_token_windows.  items = [(file_off, segment, n_tok)]:
+        source segment `segment` of the batch reads n_tok tokens (its n,
+        plus one when the document goes on) of `src_dtype` from byte
+        file_off.  Returns (groups, slow): groups = [(arena, pieces)] with
+        pieces (src_off, segment, j0, k) ready for Arena.token_pack, for
+        spans inside one arena block on the destinations' side; slow =
+        [(file_off, segment, j0, k)] for the pread + host path.  Pieces
+        split on whole tokens.  A segment that runs past the end of the
+        file is OutOfRange."""
+        from curvine_amd.native import DTYPE_ITEMSIZE
+        ss = DTYPE_ITEMSIZE[src_dtype]
+        groups: dict[int, tuple[object, list]] = {}
+        slow: list[tuple[int, int, int, int]] = []
+        for off, seg, n_tok in items:
+            if off < 0 or off + n_tok * ss > self.length:
+                raise err.OutOfRange(
+                    f"token segment at {off}: {n_tok} tokens run past the "
+                    f"file's {self.length} bytes")
+            for arena, at, e, k in self._token_parts(off, n_tok, ss,
+                                                     dst_on_device):
+                if arena is not None:
+                    groups.setdefault(arena.handle, (arena, []))[1].append(
+                        (at, seg, e, k))
+                else:
+                    slow.append((at, seg, e, k))
+        return list(groups.values()), slow
+
+    def exec_token_pack(self, groups, slow, segments, x_ptr: int, y_ptr: int,
+                        pos_ptr: int, doc_ptr: int, cu_ptr: int, rows: int,
+                        seq_len: int, src_dtype: str, dst_dtype: str,
+                        pad_id: int, ignore_index: int, vocab_size: int,
+                        dst_on_device: bool, fill: bool | None = None) -> int:
+        """Run a resolve_token_pack plan into the outputs of a packed
+        batch (`segments` as Arena.token_pack takes them; y_ptr, pos_ptr,
+        doc_ptr and cu_ptr may be 0): one Arena.token_pack per arena, which
+        also fills the pad segments and cu_seqlens, then the slow list
+        through pread -> native.token_pack_piece_host -> H2D copy or
+        memcpy, into every requested output.  With `fill` the pad
+        segments and cu_seqlens go the slow way too; by default that
+        happens when there is no arena call to do it.  A caller that
+        spreads one batch over several readers passes fill=False to all
+        but one.  Returns the tokens outside [0, vocab_size) (0 when
+        vocab_size is 0)."""
+        import struct
+
+        from curvine_amd import native
+        sc, dc = native.DTYPES[src_dtype], native.DTYPES[dst_dtype]
+        ss = native.DTYPE_ITEMSIZE[src_dtype]
+        ds = native.DTYPE_ITEMSIZE[dst_dtype]
+        bad = 0
+        for arena, pieces in groups:
+            bad += arena.token_pack(segments, pieces, x_ptr, y_ptr, pos_ptr,
+                                    doc_ptr, cu_ptr, rows, seq_len, sc, dc,
+                                    pad_id, ignore_index, vocab_size)
+        if fill is None:
+            fill = not groups
+
+        def land(parts, at, y_at):
+            x, y, pos, doc, _bad = parts
+            for out, ptr, a in ((x, x_ptr, at), (y, y_ptr, y_at),
+                                (pos, pos_ptr, at), (doc, doc_ptr, at)):
+                if ptr and out:
+                    self._land(out, ptr + a * ds, dst_on_device)
+            return _bad
+        for off, seg, j0, k in slow:
+            row, col, n, pos0, doc, _seq, flags = segments[seg]
+            raw = self.pread(off, k * ss)
+            if len(raw) != k * ss:
+                raise err.OutOfRange(
+                    f"token read at {off}: short read ({len(raw)} bytes)")
+            at = row * seq_len + col
+            bad += land(native.token_pack_piece_host(
+                raw, n, pos0, doc, flags, j0, k, sc, dc, pad_id,
+                ignore_index, vocab_size), at + j0, at + max(j0, 1) - 1)
+        if fill:
+            for row, col, n, pos0, doc, _seq, flags in segments:
+                if flags & native.TOKEN_SEG_PAD:
+                    at = row * seq_len + col
+                    land(native.token_pack_piece_host(
+                        b"", n, pos0, doc, flags, 0, n, sc, dc, pad_id,
+                        ignore_index, 0), at, at)
+            if cu_ptr:
+                cu = [0] * (len(segments) + 1)
+                for row, col, _n, _p, _d, seq, _f in segments:
+                    cu[seq] = row * seq_len + col
+                cu[len(segments)] = rows * seq_len
+                self._land(struct.pack(f"<{len(cu)}i", *cu), cu_ptr,
+                           dst_on_device)
+        return bad
+
     @staticmethod
     def _land(out: bytes, dptr: int, dst_on_device: bool) -> None:
         import ctypes

@@ -235,6 +235,63 @@ class Arena:
                                            batch, seq_len, src_dtype,
                                            dst_dtype, vocab_size)
 
+    def token_eos_index(self, spans: list[tuple[int, int, int]],
+                        src_dtype: int, eos_id: int, out_ptr: int = 0,
+                        capacity: int = 0) -> int:
+        """Where the end-of-document id occurs.  Each span (src_off, tok0,
+        n) holds n >= 1 src_dtype tokens (U16 / U32 / I32, codes from
+        DTYPES) at arena byte src_off (any alignment): tokens tok0 ..
+        tok0+n-1 of a file; spans come in ascending tok0 and do not
+        overlap.  The file indices of the tokens equal to eos_id (which is
+        non-negative and fits the dtype, so a negative I32 never matches)
+        are written to out_ptr as ascending int64, the first `capacity` of
+        them; the return value is their total, so capacity 0 (out_ptr may
+        be 0) is a pure count.  Device arena + device out_ptr = count,
+        offsets and write kernels over tiles of TOKEN_EOS_TILE tokens,
+        synchronised on return; host arena + host out_ptr = the same
+        comparison in a C++ loop.  Bad arguments raise ValueError
+        ("token eos index: ...") before anything runs."""
+        return self._n.arena_token_eos_index(self.handle, spans, src_dtype,
+                                             eos_id, out_ptr, capacity)
+
+    def token_pack(self, segments: list[tuple], pieces: list[tuple],
+                   x_ptr: int, y_ptr: int, pos_ptr: int, doc_ptr: int,
+                   cu_ptr: int, rows: int, seq_len: int, src_dtype: int,
+                   dst_dtype: int, pad_id: int, ignore_index: int = -100,
+                   vocab_size: int = 0) -> int:
+        """A document-packed batch [rows, seq_len].  A segment (row, col,
+        n, pos0, doc, seq, flags) covers columns col .. col+n-1 of `row`
+        with tokens d[0 .. n-1] of one document, plus d[n] when flags is
+        TOKEN_SEG_NEXT (the document goes on), or with padding when flags
+        is TOKEN_SEG_PAD.  For i in 0 .. n-1 of a source segment:
+        x[row, col+i] = d[i] widened (see token_windows_supported),
+        y[row, col+i] = d[i+1] when i+1 < n or NEXT, else ignore_index,
+        position_ids = pos0 + i, doc_ids = doc; of a pad segment: x =
+        pad_id, y = ignore_index, position_ids = i, doc_ids = -1.
+        cu_seqlens[seq] = row*seq_len + col for every segment and
+        cu_seqlens[len(segments)] = rows*seq_len (int32, rows*seq_len <
+        2**31).  The four [rows, seq_len] arrays are dst_dtype; every
+        pointer but x_ptr may be 0, which skips that output.
+
+        A piece (src_off, segment, j0, k) holds k >= 1 src_dtype tokens at
+        arena byte src_off (any alignment): tokens j0 .. j0+k-1 of source
+        segment `segment`'s n (+1) tokens.  Token j lands in x (and its
+        position and document id are written) when j < n, and in y one
+        column to the left when j >= 1; the piece holding token n-1 of a
+        segment without NEXT also writes its ignore_index.  Pad segments
+        and cu_seqlens are written by every call, whatever its pieces
+        cover.  Device arena + device destinations = one token_pack_kernel
+        launch, synchronised on return; host arena + host destinations =
+        the same scalar routines in C++.
+
+        With vocab_size > 0 returns how many tokens read lie outside
+        [0, vocab_size); they are still written.  Bad arguments raise
+        ValueError ("token pack: ...") before anything runs."""
+        return self._n.arena_token_pack(self.handle, segments, pieces, x_ptr,
+                                        y_ptr, pos_ptr, doc_ptr, cu_ptr, rows,
+                                        seq_len, src_dtype, dst_dtype, pad_id,
+                                        ignore_index, vocab_size)
+
     def lz4_compress(self, off: int, n: int) -> bytes:
         """Compress arena bytes [off, off+n) into a CVLZ container (HIP
         kernel on device arenas: only compressed bytes cross D2H; host
@@ -488,6 +545,36 @@ def token_docs(device: int, x_ptr: int, rows: int, seq_len: int, dtype: int,
     memory.  Bad arguments raise ValueError before anything runs."""
     return tuple(load().token_docs(device, x_ptr, rows, seq_len, dtype,
                                    eos_id, pos_ptr, doc_ptr, cu_ptr))
+
+
+# flags of a packed-batch segment (Arena.token_pack)
+TOKEN_SEG_NEXT = 1
+TOKEN_SEG_PAD = 2
+
+
+def token_eos_index_host(buf, src_dtype: int, eos_id: int, tok0: int,
+                         n: int) -> bytes:
+    """Scan `n` packed tokens, tokens tok0 .. tok0+n-1 of a file, on the
+    host with the comparison the eos-index kernels use: the file indices of
+    the tokens equal to eos_id as packed ascending int64."""
+    return load().token_eos_index_host(buf, src_dtype, eos_id, tok0, n)
+
+
+def token_pack_piece_host(buf, n: int, pos0: int, doc: int, flags: int,
+                          j0: int, k: int, src_dtype: int, dst_dtype: int,
+                          pad_id: int, ignore_index: int,
+                          vocab_size: int = 0) -> tuple:
+    """One piece of a packed batch on the host with the pack kernel's own
+    routines.  `buf` holds tokens j0 .. j0+k-1 of a source segment (n, pos0,
+    doc, flags as in Arena.token_pack); a pad segment is done whole (j0 = 0,
+    k = n, buf ignored).  Returns (x, y, pos, doc, bad): dst_dtype bytes of
+    x / position_ids / doc_ids for the segment's columns j0 ..
+    min(j0+k, n)-1 and of y for its columns from max(j0, 1)-1 on (pad: all
+    n), the ignore_index of a document that ends inside the piece included;
+    bad counts the tokens outside [0, vocab_size)."""
+    return tuple(load().token_pack_piece_host(
+        buf, n, pos0, doc, flags, j0, k, src_dtype, dst_dtype, pad_id,
+        ignore_index, vocab_size))
 
 
 def convert_host(buf, src_dtype: int, dst_dtype: int, n: int, scales=None,

@@ -1,8 +1,10 @@
-"""User-facing SDK: fsspec cv://, torch reads, safetensors load / save, and
+"""User-facing SDK: fsspec cv://, torch reads, safetensors load / save,
 CurvineTokenLoader (token-window batches; with `eos_id` and `documents` also
-position ids, doc ids and cu_seqlens per batch)."""
+position ids, doc ids and cu_seqlens per batch) and CurvinePackedTokenLoader
+(document-packed batches: whole documents per row, masked targets)."""
 from curvine_amd.sdk.fsspec_fs import CurvineFileSystemSpec  # noqa: F401
 from curvine_amd.sdk.torch_io import read_into_tensor, CurvineTensorReader  # noqa: F401
-from curvine_amd.sdk.dataset import CurvineTokenLoader  # noqa: F401
+from curvine_amd.sdk.dataset import (CurvinePackedTokenLoader,  # noqa: F401
+                                     CurvineTokenLoader, pack_segments)
 from curvine_amd.sdk.safetensors_io import (CurvineSafetensors, TensorInfo,  # noqa: F401
                                             load_file, save_file)

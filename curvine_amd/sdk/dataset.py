@@ -18,6 +18,9 @@ HBM tier:
   step in one kernel launch per batch, with a vocabulary check; on request
   also position ids, document ids and cu_seqlens under an end-of-document
   id (native.token_docs).
+* `CurvinePackedTokenLoader` — the same files as whole documents packed
+  into rows (`pack_segments`): x, targets masked at document ends, position
+  ids, document ids and cu_seqlens from one kernel launch per batch.
 
 Multiprocess loading: pass ``worker_init_fn=curvine_worker_init`` so each
 DataLoader worker builds its own client connection (connections must not
@@ -486,6 +489,358 @@ class CurvineTokenLoader:
                 ptrs.get("cu_seqlens", 0))
             if "cu_seqlens" in docs:
                 docs["cu_seqlens"] = docs["cu_seqlens"][:n_seqs + 1]
+                docs["max_seqlen"] = max_seqlen
+            yield x, y, docs
+
+    def close(self) -> None:
+        for r in self._readers:
+            r.close()
+        self._readers = []
+        self._fs.shutdown()
+
+
+# ---------------------------------------------------------------------------
+# Document-packed batches: rows made of whole documents, targets masked at
+# document ends.  The plan knows every position id, document id and sequence
+# start before a batch is launched, so one kernel writes all five tensors.
+# ---------------------------------------------------------------------------
+
+TOKEN_SEG_NEXT = 1      # native.TOKEN_SEG_NEXT: the document goes on
+TOKEN_SEG_PAD = 2       # native.TOKEN_SEG_PAD
+
+
+def pack_segments(lengths, seq_len: int, batch_size: int):
+    """First-fit packing of documents into batches of [batch_size, seq_len].
+
+    A document of L = lengths[d] tokens becomes the segments
+    [k*T, min((k+1)*T, L)) for k = 0, 1, ... with T = seq_len.  The
+    segments are taken in order; each goes contiguously after the last one
+    in the first row of the current batch with enough free columns; when no
+    row has room the batch closes and the segment opens the next one.  A
+    closed batch has batch_size rows, and every row with free columns gets
+    one pad segment at its tail (a row left empty is one pad segment).
+
+    Returns a list of batches (segments, sources), both in row-major order.
+    segments[i] = (row, col, n, pos0, doc, seq, flags) as Arena.token_pack
+    takes it: pos0 = k*T, doc the segment's ordinal within its row (0 for a
+    pad segment), seq = i, its ordinal in the batch with pad segments
+    included, flags TOKEN_SEG_NEXT when the segment does not end its
+    document, TOKEN_SEG_PAD for padding, else 0.  sources[i] = (d, k*T), or
+    None for a pad segment.  cu_seqlens of a batch is therefore
+    [row*T + col of each segment] + [batch_size*T], strictly ascending."""
+    T, B = seq_len, batch_size
+    if T <= 0 or B <= 0:
+        raise ValueError("pack_segments: seq_len and batch_size must be "
+                         "positive")
+    batches = []
+    rows: list[list] = [[] for _ in range(B)]   # (n, pos0, flags, source)
+    used = [0] * B
+    first_open = 0                 # rows before it are full
+
+    def close():
+        segments, sources = [], []
+        for r in range(B):
+            col = 0
+            for doc, (n, pos0, flags, src) in enumerate(rows[r]):
+                segments.append((r, col, n, pos0, doc, len(segments), flags))
+                sources.append(src)
+                col += n
+            if col < T:
+                segments.append((r, col, T - col, 0, 0, len(segments),
+                                 TOKEN_SEG_PAD))
+                sources.append(None)
+        batches.append((segments, sources))
+
+    for d, L in enumerate(lengths):
+        for t0 in range(0, L, T):
+            n = min(T, L - t0)
+            flags = TOKEN_SEG_NEXT if t0 + n < L else 0
+            while True:
+                while first_open < B and used[first_open] == T:
+                    first_open += 1
+                row = next((r for r in range(first_open, B)
+                            if T - used[r] >= n), None)
+                if row is not None:
+                    break
+                close()
+                rows = [[] for _ in range(B)]
+                used = [0] * B
+                first_open = 0
+            rows[row].append((n, t0, flags, (d, t0)))
+            used[row] += n
+    if any(used):
+        close()
+    return batches
+
+
+class CurvinePackedTokenLoader:
+    """Document-packed batches from flat token-id files: yields (x, y,
+    docs) with x and y two contiguous [batch_size, seq_len] tensors of
+    ``out_dtype`` on ``device``, fresh every batch and complete when
+    yielded.
+
+    A document of file f is a maximal run of tokens that ends with
+    ``eos_id``; the tokens after the last eos_id form one more,
+    unterminated, document when there are any.  Documents never cross
+    files.  The index is built once, here: one
+    SyncLocalReader.token_eos_index per file (device kernels for HBM-tier
+    files with a cuda device).
+
+    The documents are taken in file order, or with ``shuffle`` under
+    random.Random(seed + epoch).shuffle (``set_epoch``); the list is cut to
+    a multiple of ``world`` and rank r takes order[r::world].  They are
+    packed by ``pack_segments``: whole documents side by side in a row,
+    documents longer than seq_len in chunks of seq_len whose position ids
+    continue, padding at the row tails.  y[r, c] is the next token of the
+    same document, and ``ignore_index`` at a document's last token and in
+    padding; x is ``pad_id`` (default eos_id) in padding.
+
+    docs holds the requested ``outputs``: position_ids and doc_ids
+    ([batch_size, seq_len] of ``out_dtype``; doc_ids count the segments
+    of a row from 0 and are -1 in padding, position_ids count from 0 in
+    padding), cu_seqlens (int32, one entry per segment in row-major order,
+    pad segments included, then batch_size * seq_len) and with it
+    "max_seqlen", an int.  All of them are known when the batch is
+    planned: nothing is scanned per batch and no result word comes back,
+    other than the vocabulary count when ``vocab_size`` > 0 (a batch
+    holding a token outside [0, vocab_size) raises InvalidArgument).
+
+    len(loader) is the minimum over all ranks of their batch counts: every
+    rank computes the packing (not the block resolution) of every rank, so
+    that all ranks take the same number of steps; a rank with more batches
+    drops its last ones.
+
+    HBM-tier files + cuda device = one token_pack_kernel launch per arena
+    per batch; MEM tier + cpu device = its host twin; anything else (file
+    tier, MEM tier + cuda device, tokens cut by a block boundary) goes
+    through pread and the host routine.  A batch's plan is resolved when
+    the batch is first drawn, once per order, and replayed from then on; the
+    readers stay open, which pins their blocks, until close()."""
+
+    def __init__(self, conf: ClusterConf, paths: list[str], seq_len: int,
+                 batch_size: int, eos_id: int, device: str = "cuda:0",
+                 src_dtype: str = "U16", out_dtype=None,
+                 header_bytes: int = 0, pad_id: int | None = None,
+                 ignore_index: int = -100,
+                 outputs: tuple[str, ...] = TOKEN_DOCUMENT_OUTPUTS,
+                 shuffle: bool = False, seed: int = 0, rank: int = 0,
+                 world: int = 1, vocab_size: int = 0):
+        import torch
+
+        from curvine_amd import errors as err
+        from curvine_amd import native
+        from curvine_amd.client.filesystem import SyncFs
+        from curvine_amd.client.reader import SyncLocalReader
+        out_dtype = torch.int64 if out_dtype is None else out_dtype
+        dst_dtype = {torch.int64: "I64", torch.int32: "I32"}.get(out_dtype)
+        if dst_dtype is None or \
+                not native.token_windows_supported(src_dtype, dst_dtype):
+            raise err.Unsupported(
+                f"packed token loader: {src_dtype} -> {out_dtype} is not a "
+                "supported pair")
+        for name, v in (("seq_len", seq_len), ("batch_size", batch_size)):
+            if not isinstance(v, int) or v <= 0:
+                raise err.InvalidArgument(
+                    f"packed token loader: {name} must be a positive integer")
+        if world <= 0 or not 0 <= rank < world:
+            raise err.InvalidArgument(
+                f"packed token loader: rank {rank} of world {world}")
+        if header_bytes < 0:
+            raise err.InvalidArgument(
+                "packed token loader: negative header_bytes")
+        if vocab_size < 0:
+            raise err.InvalidArgument(
+                "packed token loader: negative vocab_size")
+        outputs = tuple(outputs)
+        for name in outputs:
+            if name not in TOKEN_DOCUMENT_OUTPUTS:
+                raise err.InvalidArgument(
+                    f"packed token loader: unknown output {name!r}")
+        src_top = {"U16": 2 ** 16, "U32": 2 ** 32, "I32": 2 ** 31}[src_dtype]
+        if not isinstance(eos_id, int) or not 0 <= eos_id < src_top:
+            raise err.InvalidArgument(
+                f"packed token loader: eos_id must be a non-negative "
+                f"{src_dtype} value")
+        if vocab_size > 0 and eos_id >= vocab_size:
+            raise err.InvalidArgument(
+                f"packed token loader: eos_id {eos_id} outside "
+                f"[0, {vocab_size})")
+        pad_id = eos_id if pad_id is None else pad_id
+        info = torch.iinfo(out_dtype)
+        for name, v in (("pad_id", pad_id), ("ignore_index", ignore_index)):
+            if not isinstance(v, int) or not info.min <= v <= info.max:
+                raise err.InvalidArgument(
+                    f"packed token loader: {name} does not fit {out_dtype}")
+        if "cu_seqlens" in outputs and batch_size * seq_len >= 2 ** 31:
+            raise err.InvalidArgument(
+                "packed token loader: cu_seqlens needs batch_size * seq_len "
+                "below 2**31")
+        self.device = device
+        self.seq_len = seq_len
+        self.batch_size = batch_size
+        self.eos_id = eos_id
+        self.src_dtype = src_dtype
+        self.dst_dtype = dst_dtype
+        self.out_dtype = out_dtype
+        self.header_bytes = header_bytes
+        self.pad_id = pad_id
+        self.ignore_index = ignore_index
+        self.outputs = outputs
+        self.shuffle = shuffle
+        self.seed = seed
+        self.rank = rank
+        self.world = world
+        self.vocab_size = vocab_size
+        self.epoch = 0
+        self._on_dev = torch.device(device).type != "cpu"
+        self._fs = SyncFs(conf)
+        self._readers = []
+        self._docs = []                # (reader_idx, first token, tokens)
+        self._packs = None             # (order key, per-rank batches)
+        self._plans = None             # (order key, batch plans)
+        item = native.DTYPE_ITEMSIZE[src_dtype]
+        try:
+            for p in paths:
+                fb = self._fs.call(self._fs.fs.client.open(p))
+                ridx = len(self._readers)
+                self._readers.append(SyncLocalReader(fb))
+                body = fb.status.length - header_bytes
+                if body < 0 or body % item:
+                    raise err.InvalidArgument(
+                        f"packed token loader: {p} is {fb.status.length} "
+                        f"bytes, not a {header_bytes}-byte header plus whole "
+                        f"{src_dtype} tokens")
+                start = 0
+                for e in self._readers[ridx].token_eos_index(
+                        src_dtype, header_bytes, eos_id, self._on_dev):
+                    self._docs.append((ridx, start, e + 1 - start))
+                    start = e + 1
+                if start < body // item:
+                    self._docs.append((ridx, start, body // item - start))
+        except Exception:
+            self.close()
+            raise
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = epoch
+
+    @property
+    def num_documents(self) -> int:
+        """Documents in all files."""
+        return len(self._docs)
+
+    def _key(self):
+        return self.epoch if self.shuffle else None
+
+    def _order(self, rank: int) -> list[int]:
+        order = list(range(len(self._docs)))
+        if self.shuffle:
+            import random
+            random.Random(self.seed + self.epoch).shuffle(order)
+        order = order[:len(order) - len(order) % self.world]
+        return order[rank::self.world]
+
+    def _pack(self):
+        """(this rank's documents, its batches cut to the common length)"""
+        if self._packs is None or self._packs[0] != self._key():
+            mine, batches, n = None, None, None
+            for r in range(self.world):
+                order = self._order(r)
+                packed = pack_segments([self._docs[d][2] for d in order],
+                                       self.seq_len, self.batch_size)
+                n = len(packed) if n is None else min(n, len(packed))
+                if r == self.rank:
+                    mine, batches = order, packed
+            self._packs = (self._key(), mine, batches[:n])
+        return self._packs[1], self._packs[2]
+
+    def __len__(self) -> int:
+        return len(self._pack()[1])
+
+    @property
+    def pack_efficiency(self) -> float:
+        """Non-pad columns over all columns of this rank's epoch."""
+        batches = self._pack()[1]
+        if not batches:
+            return 0.0
+        real = sum(s[2] for segments, _src in batches for s in segments
+                   if not s[6] & TOKEN_SEG_PAD)
+        return real / (len(batches) * self.batch_size * self.seq_len)
+
+    def _plan(self, b: int):
+        """The plan of batch b with every segment resolved down to arena
+        pieces (valid while the readers stay open), made when the batch is
+        first drawn and kept: iteration is torch.empty and replayed
+        exec_token_pack calls."""
+        from curvine_amd import native
+        item = native.DTYPE_ITEMSIZE[self.src_dtype]
+        order, batches = self._pack()
+        segments, sources = batches[b]
+        T = self.seq_len
+        per_reader: dict[int, list] = {}
+        for i, (seg, src) in enumerate(zip(segments, sources)):
+            if src is None:
+                continue
+            ridx, start, _len = self._docs[order[src[0]]]
+            off = self.header_bytes + (start + src[1]) * item
+            per_reader.setdefault(ridx, []).append(
+                (off, i, seg[2] + (seg[6] & TOKEN_SEG_NEXT)))
+        merged: dict[int, tuple[object, list]] = {}
+        slows = []
+        for ridx, items in per_reader.items():
+            r = self._readers[ridx]
+            groups, slow = r.resolve_token_pack(items, self.src_dtype,
+                                                self._on_dev)
+            for arena, pieces in groups:
+                merged.setdefault(arena.handle, (arena, []))[1].extend(pieces)
+            slows.append((r, slow))
+        # one arena call per arena per batch, made through the first reader;
+        # it (or, without one, the first reader's slow path) also fills the
+        # padding and cu_seqlens
+        execs = [(r, list(merged.values()) if k == 0 else [], slow,
+                  None if k == 0 else False)
+                 for k, (r, slow) in enumerate(slows)]
+        cu = [s[0] * T + s[1] for s in segments] + [self.batch_size * T]
+        max_seqlen = max(b - a for a, b in zip(cu, cu[1:]))
+        return segments, execs, max_seqlen
+
+    def __iter__(self):
+        import torch
+
+        from curvine_amd import errors as err
+        dev = torch.device(self.device)
+        if self._plans is None or self._plans[0] != self._key():
+            self._plans = (self._key(), [None] * len(self))
+        plans = self._plans[1]
+        B, T = self.batch_size, self.seq_len
+        for b in range(len(plans)):
+            if plans[b] is None:
+                plans[b] = self._plan(b)
+            segments, execs, max_seqlen = plans[b]
+            x = torch.empty((B, T), dtype=self.out_dtype, device=dev)
+            y = torch.empty((B, T), dtype=self.out_dtype, device=dev)
+            docs = {}
+            for name in self.outputs:
+                if name == "cu_seqlens":
+                    docs[name] = torch.empty(len(segments) + 1,
+                                             dtype=torch.int32, device=dev)
+                else:
+                    docs[name] = torch.empty((B, T), dtype=self.out_dtype,
+                                             device=dev)
+            ptrs = {k: t.data_ptr() for k, t in docs.items()}
+            bad = 0
+            for reader, groups, slow, fill in execs:
+                bad += reader.exec_token_pack(
+                    groups, slow, segments, x.data_ptr(), y.data_ptr(),
+                    ptrs.get("position_ids", 0), ptrs.get("doc_ids", 0),
+                    ptrs.get("cu_seqlens", 0), B, T, self.src_dtype,
+                    self.dst_dtype, self.pad_id, self.ignore_index,
+                    self.vocab_size, self._on_dev, fill)
+            if bad:
+                raise err.InvalidArgument(
+                    f"packed token loader: {bad} token ids outside "
+                    f"[0, {self.vocab_size}) in batch {b}")
+            if "cu_seqlens" in docs:
                 docs["max_seqlen"] = max_seqlen
             yield x, y, docs
 
