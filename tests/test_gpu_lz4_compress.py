@@ -1,17 +1,20 @@
 """GPU tests (MI355X) for the device LZ4 compressor and the LZ4 replication
 push between HBM tiers.
 
-The host decoder (native.lz4_decompress) is the oracle for bytes; the strict
-checker in lz4_checks.py enforces the LZ4 end-of-block rules on what the
-kernel emits.
+The pure-Python decoder (kernel_refs.cvlz_decode_ref) is the oracle for
+bytes, and the host decoder (native.lz4_decompress) must agree with it; the
+strict checker in lz4_checks.py enforces the LZ4 end-of-block rules on what
+the kernel emits.  The crafted edge cases are in
+test_gpu_lz4_compress_edges.py.
 """
 import asyncio
-import os
 
 import pytest
 
 from curvine_amd import native
-from lz4_checks import CHUNK, pattern, strict_check, text8, worst_case
+from kernel_refs import cvlz_decode_ref
+from lz4_checks import (CHUNK, pattern, rand_bytes, strict_check, text8,
+                        worst_case)
 
 pytestmark = pytest.mark.gpu
 
@@ -27,11 +30,11 @@ SIZE_MARGIN = 0.00027
 
 def _period1_then_random(n):
     tail = min(n, 1000)
-    return b"\xa5" * (n - tail) + os.urandom(tail)
+    return b"\xa5" * (n - tail) + rand_bytes(tail, 31)
 
 
 def _repeat_32k(n):
-    half = os.urandom(32768)
+    half = rand_bytes(32768, 32)
     return (half * (n // 32768 + 1))[:n]
 
 
@@ -41,7 +44,7 @@ def _far_offset(n):
     the largest offset a block can hold, so this sits next to the format's
     limit.  The same bytes recur at 65535 as well, straddling the chunk
     boundary, where no match may be made."""
-    b = bytearray(os.urandom(n))
+    b = bytearray(rand_bytes(n, 33))
     for c in range(0, n, CHUNK):
         if c + 65520 <= n:
             b[c + 65500:c + 65520] = b[c:c + 20]
@@ -52,7 +55,7 @@ def _far_offset(n):
 
 KINDS = {
     "zeros": lambda n: bytes(n),
-    "urandom": lambda n: os.urandom(n),
+    "urandom": lambda n: rand_bytes(n, 34),
     "text8": text8,
     "pattern123": pattern,
     "period1_then_random": _period1_then_random,
@@ -87,6 +90,7 @@ def test_compress_matrix(arena, kind, off):
             arena.write(off, data, 0, n)
         c = arena.lz4_compress(off, n)
         strict_check(c, n)
+        assert cvlz_decode_ref(c) == data, f"{kind} n={n} off={off}"
         assert native.lz4_decompress(c) == data, f"{kind} n={n} off={off}"
         assert len(c) <= worst_case(n), f"{kind} n={n}: {len(c)}"
 
@@ -146,7 +150,7 @@ def test_range_checks(arena):
 def test_replication_hbm_to_hbm(tmp_path):
     from curvine_amd.testing import MiniCluster, test_conf
 
-    data = text8(2 << 20, seed=11) + os.urandom(1 << 20)
+    data = text8(2 << 20, seed=11) + rand_bytes(1 << 20, 35)
 
     async def main():
         conf = test_conf(str(tmp_path))

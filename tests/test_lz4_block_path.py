@@ -3,8 +3,10 @@ lz4_decompress_into on a host arena, BlockReader.read_lz4 /
 BlockWriter.write_lz4 on MEM and SSD tiers, the WriteBlockLz4 stream and
 the LZ4 replication push between two workers.
 
-The host decoder (native.lz4_decompress) is the oracle for bytes; the strict
-checker (lz4_checks.py) enforces the LZ4 end-of-block rules.
+The pure-Python decoder (kernel_refs.cvlz_decode_ref) is the oracle for
+bytes, and the host decoder (native.lz4_decompress) must agree with it; the
+strict checker (lz4_checks.py) enforces the LZ4 end-of-block rules.  The
+crafted edge cases of the host compressor are in test_lz4_compress_cases.py.
 """
 import asyncio
 import os
@@ -13,7 +15,8 @@ import struct
 import pytest
 
 from curvine_amd import native
-from lz4_checks import (CPU_KINDS, strict_check, text8,
+from kernel_refs import cvlz_decode_ref
+from lz4_checks import (CPU_KINDS, rand_bytes, strict_check, text8,
                         zero_first_match_offset)
 
 SIZES = (0, 1, 12, 13, 65535, 65536, 65537, 2 * 65536 + 13)
@@ -35,6 +38,7 @@ def test_host_arena_compress(host_arena, kind):
             host_arena.write(OFF, data, 0, n)
         c = host_arena.lz4_compress(OFF, n)
         strict_check(c, n)
+        assert cvlz_decode_ref(c) == data, f"{kind} n={n}"
         assert native.lz4_decompress(c) == data, f"{kind} n={n}"
 
 
@@ -78,7 +82,7 @@ def test_block_read_write_lz4(tmp_path, tier):
         data_dirs=[f"[{tier}:{size}]{tmp_path}/{tier.lower()}"]))
     try:
         seg = (1 << 20) + 5
-        src = text8(2 * seg, seed=3) + os.urandom(seg)
+        src = text8(2 * seg, seed=3) + rand_bytes(seg, 36)
         w = store.create_writer(1, 4 << 20, tier)
         for i in range(3):
             c = native.lz4_compress(src[i * seg:(i + 1) * seg])
@@ -94,6 +98,7 @@ def test_block_read_write_lz4(tmp_path, tier):
                 c = r.read_lz4(off, n)
                 want = src[off:off + n]
                 strict_check(c, len(want))
+                assert cvlz_decode_ref(c) == want
                 assert native.lz4_decompress(c) == want
         finally:
             r.close()
@@ -132,7 +137,7 @@ def test_replication_codec_setting():
 # two workers
 # ---------------------------------------------------------------------------
 
-MIXED = text8(2 << 20, seed=11) + os.urandom(1 << 20)
+MIXED = text8(2 << 20, seed=11) + rand_bytes(1 << 20, 37)
 
 
 def _run(tmp_path, codec, body):
