@@ -20,6 +20,8 @@
 
 #include <algorithm>
 #include <atomic>
+#include <cfloat>
+#include <cmath>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -156,6 +158,7 @@ static uint32_t crc32c_combine(uint32_t crc1, uint32_t crc2, uint64_t len2) {
 #include "token_gather.hip"
 #include "token_docs.hip"
 #include "token_pack.hip"
+#include "array_gather.hip"
 
 // ---------------------------------------------------------------------------
 // GPU availability
@@ -1689,6 +1692,179 @@ static uintptr_t arena_base_ptr(int h) {
   return (uintptr_t)get_arena(h)->base;
 }
 
+// ---- array samples (array_gather.hip) ----
+//
+// Pieces: (src_off, row, e0, n): n source bytes at arena byte src_off are
+// bytes e0 .. e0+n-1 of sample `row` of `batch` samples of H*W*C uint8, HWC
+// order.  rows[b] = (dy, dx, flip) places the hc x wc crop of sample b; the
+// element of output row r, column q, channel c is source pixel (dy + r,
+// dx + (flip ? wc-1-q : q)) times scale[c] plus bias[c], as dst_dt, in a
+// dense NCHW (layout 0) or NHWC (layout 1) array at out_ptr.  Every argument
+// error is raised here, on the host, before anything runs.
+typedef std::tuple<uint64_t, uint64_t, uint64_t, uint64_t> ArrayPieceTuple;
+typedef std::tuple<uint64_t, uint64_t, uint64_t> ArrayRowTuple;
+typedef std::tuple<uint64_t, uint64_t, uint64_t> ArrayDims;
+typedef std::tuple<uint64_t, uint64_t> ArrayCrop;
+
+// shape, crop, normalisation, dtype and layout of a call; returns the bytes
+// of one sample, sets `out_el` to the elements of one sample's output
+static uint64_t array_check_shape(const char* who_is, ArrayDims shape,
+                                  ArrayCrop crop,
+                                  const std::vector<double>& scale,
+                                  const std::vector<double>& bias,
+                                  uint64_t ddt, uint64_t layout,
+                                  ArrayShape& p, uint64_t& out_el) {
+  const std::string who = who_is;
+  if (ddt >= DT_COUNT)
+    throw std::invalid_argument(who + ": unknown dtype code");
+  if (!array_dst_supported((uint32_t)ddt))
+    throw std::invalid_argument(who + ": unsupported destination dtype");
+  if (layout != ARRAY_NCHW && layout != ARRAY_NHWC)
+    throw std::invalid_argument(who + ": unknown layout");
+  uint64_t H = std::get<0>(shape), W = std::get<1>(shape),
+           C = std::get<2>(shape);
+  uint64_t hc = std::get<0>(crop), wc = std::get<1>(crop);
+  if (C < 1 || C > 4)
+    throw std::invalid_argument(who + ": channels outside 1..4");
+  if (H == 0 || W == 0 || hc == 0 || wc == 0)
+    throw std::invalid_argument(who + ": zero dimension");
+  if (hc > H || wc > W)
+    throw std::invalid_argument(who + ": crop larger than the source");
+  uint64_t sb;
+  if (__builtin_mul_overflow(H, W, &sb) || __builtin_mul_overflow(sb, C, &sb) ||
+      sb >= (1ull << 31))
+    throw std::invalid_argument(who + ": sample size overflows");
+  if (scale.size() != C || bias.size() != C)
+    throw std::invalid_argument(who + ": scale and bias need one entry per channel");
+  p = ArrayShape{(uint32_t)H, (uint32_t)W, (uint32_t)C, (uint32_t)hc,
+                 (uint32_t)wc, (uint32_t)layout, {0, 0, 0, 0}, {0, 0, 0, 0}};
+  for (uint64_t c = 0; c < C; ++c) {
+    // finite as f32 too: checked before the narrowing
+    if (!(std::fabs(scale[c]) <= FLT_MAX) || !(std::fabs(bias[c]) <= FLT_MAX))
+      throw std::invalid_argument(who + ": scale or bias is not finite");
+    p.scale[c] = (float)scale[c];
+    p.bias[c] = (float)bias[c];
+  }
+  out_el = hc * wc * C;                          // <= sb
+  return sb;
+}
+
+static ArrayRow array_check_row(const char* who_is, const ArrayRowTuple& t,
+                                const ArrayShape& p) {
+  const std::string who = who_is;
+  uint64_t dy = std::get<0>(t), dx = std::get<1>(t), flip = std::get<2>(t);
+  if (dy > p.H - p.h || dx > p.W - p.w)
+    throw std::invalid_argument(who + ": crop runs past the sample");
+  if (flip > 1)
+    throw std::invalid_argument(who + ": flip is not 0 or 1");
+  return ArrayRow{(uint32_t)dy, (uint32_t)dx, (uint32_t)flip};
+}
+
+static void arena_array_samples(int h, std::vector<ArrayPieceTuple> pieces_in,
+                                std::vector<ArrayRowTuple> rows_in,
+                                uintptr_t out_ptr, uint64_t batch,
+                                ArrayDims shape, ArrayCrop crop,
+                                std::vector<double> scale,
+                                std::vector<double> bias, uint64_t ddt,
+                                uint64_t layout) {
+  const char* who = "array samples";
+  Arena* a = get_arena(h);
+  ArrayShape p;
+  uint64_t out_el;
+  uint64_t sb = array_check_shape(who, shape, crop, scale, bias, ddt, layout,
+                                  p, out_el);
+  if (batch == 0)
+    throw std::invalid_argument("array samples: batch must be positive");
+  if (rows_in.size() != batch)
+    throw std::invalid_argument("array samples: one (dy, dx, flip) per sample");
+  uint64_t ds = cast_itemsize((uint32_t)ddt), n_el, dst_b, out_end;
+  if (__builtin_mul_overflow(batch, out_el, &n_el) ||
+      __builtin_mul_overflow(n_el, ds, &dst_b) ||
+      __builtin_add_overflow((uint64_t)out_ptr, dst_b, &out_end))
+    throw std::invalid_argument("array samples: destination size overflows");
+  if (out_ptr == 0 || out_ptr % ds)
+    throw std::invalid_argument("array samples: out_ptr null or misaligned");
+  std::vector<ArrayRow> rows;
+  rows.reserve(rows_in.size());
+  for (auto& t : rows_in) rows.push_back(array_check_row(who, t, p));
+  std::vector<ArrayPiece> pieces;
+  pieces.reserve(pieces_in.size());
+  for (auto& t : pieces_in) {
+    ArrayPiece g{std::get<0>(t), std::get<1>(t), std::get<2>(t), std::get<3>(t)};
+    uint64_t last, end;
+    if (g.n == 0)
+      throw std::invalid_argument("array samples: piece without bytes");
+    if (g.row >= batch)
+      throw std::invalid_argument("array samples: piece row outside the batch");
+    if (__builtin_add_overflow(g.e0, g.n, &last) ||
+        __builtin_add_overflow(g.src_off, g.n, &end))
+      throw std::invalid_argument("array samples: piece range overflows");
+    if (last > sb)
+      throw std::invalid_argument("array samples: piece runs past its sample");
+    if (end > a->cap)
+      throw std::invalid_argument("array samples: arena range out of bounds");
+    pieces.push_back(g);
+  }
+  py::gil_scoped_release rel;
+  uint8_t* out = (uint8_t*)out_ptr;
+  if (!a->is_dev()) {
+    // a host arena scatters with the CPU: device memory is the wrong side
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, (const void*)out_ptr) != hipSuccess)
+      (void)hipGetLastError();   // plain host memory, or no runtime
+    else if (at.type == hipMemoryTypeDevice)
+      throw std::invalid_argument(
+          "array samples: device destination on a host arena");
+    for (auto& g : pieces)
+      array_samples_host((const uint8_t*)a->base, g, rows.data(), out, p,
+                         (uint32_t)ddt);
+    return;
+  }
+  Tiles tiles = build_tiles(
+      pieces.size(), [&](size_t i) { return pieces[i].n; },
+      [](size_t) { return (uint64_t)ARRAY_TILE; }, who);
+  std::lock_guard<std::mutex> g(a->mu);
+  HIP_CHECK(hipSetDevice(a->device));
+  std::vector<std::pair<uint64_t, uint64_t>> known;
+  check_device_range(a->device, out_ptr, out_end, who, "out_ptr",
+                     "destination", known);
+  if (tiles.empty()) return;   // nothing to gather: no grid-0 launch
+  Scratch sc(a, Scratch::room<ArrayRow>(rows.size()) +
+                    tiles.room<ArrayPiece>(pieces.size()));
+  DevTiles<ArrayPiece> d = upload_tiles(a, sc, pieces, tiles);
+  ArrayRow* d_rows = sc.take<ArrayRow>(rows.size());
+  HIP_CHECK(hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(ArrayRow),
+                           hipMemcpyHostToDevice, a->kstream));
+  launch(array_samples_kernel, d.grid(), WG, a->kstream,
+         (const uint8_t*)a->base, d.items, d.tile_item, d.tile_off, d.n_tiles,
+         (const ArrayRow*)d_rows, out, p, (uint32_t)ddt);
+  HIP_CHECK(hipStreamSynchronize(a->kstream));
+}
+
+// one whole sample on the host (the slow path of the array reader: samples
+// with a part in the file tier, across sides or in a hole go through the
+// kernel's own scalar routine): its dense hc*wc*C output as bytes
+static py::bytes array_sample_host_py(py::buffer src, uint64_t dy, uint64_t dx,
+                                      uint64_t flip, ArrayDims shape,
+                                      ArrayCrop crop, std::vector<double> scale,
+                                      std::vector<double> bias, uint64_t ddt,
+                                      uint64_t layout) {
+  const char* who = "array sample";
+  py::buffer_info bi = src.request();
+  ArrayShape p;
+  uint64_t out_el;
+  uint64_t sb = array_check_shape(who, shape, crop, scale, bias, ddt, layout,
+                                  p, out_el);
+  ArrayRow a = array_check_row(who, ArrayRowTuple(dy, dx, flip), p);
+  if (sb > (uint64_t)bi.size * bi.itemsize)
+    throw std::invalid_argument("array sample: source shorter than the sample");
+  uint64_t out_b = out_el * cast_itemsize((uint32_t)ddt);
+  std::vector<uint32_t> out(out_b / 4 + 1);    // aligned for both itemsizes
+  array_sample_host((const uint8_t*)bi.ptr, a, (uint8_t*)out.data(), p,
+                    (uint32_t)ddt);
+  return py::bytes((const char*)out.data(), out_b);
+}
+
 // batched small reads (the fio iodepth>1 analog): issue every copy async
 // on the caller's thread-local stream, sync ONCE — amortizes launch+sync
 // cost over the batch (4K random-read IOPS path)
@@ -2365,6 +2541,8 @@ PYBIND11_MODULE(_native, m) {
         py::arg("scale_every") = 0, py::arg("scale_e0") = 0);
   m.def("arena_token_windows", &arena_token_windows);
   m.def("token_convert_host", &token_convert_host);
+  m.def("arena_array_samples", &arena_array_samples);
+  m.def("array_sample_host", &array_sample_host_py);
   m.def("absmax_scales", &absmax_scales);
   m.def("token_docs", &token_docs);
   m.def("arena_token_eos_index", &arena_token_eos_index);
@@ -2456,6 +2634,7 @@ PYBIND11_MODULE(_native, m) {
   m.attr("CRC_SUB") = CRC_SUB;
   m.attr("CAST_TILE") = CAST_TILE;
   m.attr("TOKEN_TILE") = TOKEN_TILE;
+  m.attr("ARRAY_TILE") = ARRAY_TILE;
   m.attr("TOKEN_DOC_CHUNK") = TOKEN_DOC_CHUNK;
   m.attr("TOKEN_EOS_TILE") = TOKEN_EOS_TILE;
   m.attr("TOKEN_PACK_TILE") = TOKEN_PACK_TILE;

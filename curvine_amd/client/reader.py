@@ -561,6 +561,82 @@ class SyncLocalReader:
                            if v < 0 or v >= vocab_size)
         return bad
 
+    # ---------------- array samples ----------------
+    def resolve_array_samples(self, samples, sample_bytes: int,
+                              dst_on_device: bool):
+        """Resolution half of an array-sample batch, modelled on
+        resolve_token_windows.  samples = [(file_off, row)]: sample `row`
+        is sample_bytes uint8 bytes starting at byte file_off.  Returns
+        (groups, slow): groups = [(arena, pieces)] with pieces (src_off,
+        row, e0, n) ready for Arena.array_samples, one per arena block the
+        sample touches, for samples whose every byte sits in arena blocks on
+        the destination's side; slow = [(file_off, row)] for samples with a
+        part elsewhere (file tier, cross-side arena, a hole), which go
+        through pread and the host routine as a whole.  A sample that runs
+        past the end of the file is OutOfRange."""
+        import bisect
+        groups: dict[int, tuple[object, list]] = {}
+        slow: list[tuple[int, int]] = []
+        blocks = self.fb.blocks
+        for off, row in samples:
+            if off < 0 or off + sample_bytes > self.length:
+                raise err.OutOfRange(
+                    f"array sample at {off}: {sample_bytes} bytes run past "
+                    f"the file's {self.length} bytes")
+            parts = []
+            e = 0
+            while e < sample_bytes:
+                p = off + e
+                if _hole_span(self._offs, blocks, self.length, p) > 0:
+                    parts = None
+                    break
+                idx = bisect.bisect_right(self._offs, p) - 1
+                lb = blocks[idx]
+                r = self._readers[idx]
+                arena = getattr(r.layout, "arena", None)
+                same_side = r.meta.get("kind") == "arena" and \
+                    arena is not None and \
+                    ((arena.device >= 0) == bool(dst_on_device))
+                if not same_side:
+                    parts = None
+                    break
+                k = min(sample_bytes - e, lb.offset + lb.block.length - p)
+                parts.append((arena, (r.meta["offset"] + p - lb.offset, row,
+                                      e, k)))
+                e += k
+            if parts is None:
+                slow.append((off, row))
+                continue
+            for arena, piece in parts:
+                groups.setdefault(arena.handle, (arena, []))[1].append(piece)
+        return list(groups.values()), slow
+
+    def exec_array_samples(self, groups, slow, out_ptr: int, batch: int,
+                           rows, shape, crop, scale, bias, dst_dtype: str,
+                           layout: str, dst_on_device: bool) -> None:
+        """Run a resolve_array_samples plan into a dense [batch, C, h, w]
+        (or [batch, h, w, C]) array of dst_dtype at out_ptr, rows[b] = (dy,
+        dx, flip): one Arena.array_samples per arena, then every slow sample
+        through pread -> native.array_sample_host (the kernel's own routine)
+        -> H2D copy or memcpy into its contiguous C*h*w range."""
+        from curvine_amd import native
+        dc = native.DTYPES[dst_dtype]
+        H, W, C = shape
+        for arena, pieces in groups:
+            arena.array_samples(pieces, rows, out_ptr, batch, shape, crop,
+                                scale, bias, dc, layout)
+        sample_bytes = H * W * C
+        out_b = C * crop[0] * crop[1] * native.DTYPE_ITEMSIZE[dst_dtype]
+        for off, row in slow:
+            raw = self.pread(off, sample_bytes)
+            if len(raw) != sample_bytes:
+                raise err.OutOfRange(
+                    f"array read at {off}: short read ({len(raw)} bytes)")
+            dy, dx, flip = rows[row]
+            out = native.array_sample_host(raw, dy, dx, flip, shape, crop,
+                                           scale, bias, dc, layout)
+            self._land(out, out_ptr + row * out_b, dst_on_device)
+
     # ---------------- document-packed token batches ----------------
     def _token_parts(self, off: int, n_tok: int, ss: int,
                      dst_on_device: bool):

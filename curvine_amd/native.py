@@ -235,6 +235,36 @@ class Arena:
                                            batch, seq_len, src_dtype,
                                            dst_dtype, vocab_size)
 
+    def array_samples(self, pieces: list[tuple[int, int, int, int]],
+                      rows: list[tuple[int, int, int]], out_ptr: int,
+                      batch: int, shape: tuple[int, int, int],
+                      crop: tuple[int, int], scale, bias, dst_dtype: int,
+                      layout: str = "NCHW") -> None:
+        """Array-sample gather: `batch` samples of shape = (H, W, C) uint8
+        bytes each, HWC order, 1 <= C <= 4, become one dense array of
+        dst_dtype (F32 / F16 / BF16, see array_samples_supported; codes from
+        DTYPES) at `out_ptr`, [batch, C, h, w] for layout "NCHW" or
+        [batch, h, w, C] for "NHWC", with crop = (h, w).  rows[b] = (dy, dx,
+        flip) places sample b's crop: output row r, column q, channel c is
+        source pixel (dy + r, dx + (w-1-q if flip else q)), as
+        f32(f32(v) * scale[c]) + bias[c] rounded to f32, the two steps never
+        fused, then cast; scale and bias hold C finite floats, used as
+        float32.  Each piece (src_off, row, e0, n) holds n >= 1 source bytes
+        at arena byte src_off (any alignment): bytes e0 .. e0+n-1 of sample
+        `row`; pieces may cut a sample anywhere.  Every source byte inside
+        the crop is converted once; elements whose byte is in no piece are
+        not written.  out_ptr is aligned to the itemsize only.  Device
+        arena + device destination = one array_samples_kernel launch over
+        tiles of ARRAY_TILE bytes, synchronised on return; host arena + host
+        destination = the same scalar routines in C++.  Bad dtypes, shapes,
+        crops, rows, pieces, ranges, alignment and a destination on the
+        wrong side raise ValueError before anything runs."""
+        self._n.arena_array_samples(self.handle, pieces, rows, out_ptr, batch,
+                                    tuple(shape), tuple(crop),
+                                    [float(v) for v in scale],
+                                    [float(v) for v in bias], dst_dtype,
+                                    array_layout_code(layout))
+
     def token_eos_index(self, spans: list[tuple[int, int, int]],
                         src_dtype: int, eos_id: int, out_ptr: int = 0,
                         capacity: int = 0) -> int:
@@ -524,6 +554,36 @@ def token_convert_host(buf, src_dtype: int, dst_dtype: int, n: int) -> bytes:
     """Widen `n` packed tokens on the host with the routine the
     token_windows kernel uses: the widened bytes."""
     return load().token_convert_host(buf, src_dtype, dst_dtype, n)
+
+
+# array samples: uint8 image arrays read as normalised float tensors
+ARRAY_TARGETS = ("F32", "F16", "BF16")
+ARRAY_LAYOUTS = {"NCHW": 0, "NHWC": 1}
+
+
+def array_samples_supported(dst: str) -> bool:
+    """Arena.array_samples writes `dst` tensors."""
+    return dst in ARRAY_TARGETS
+
+
+def array_layout_code(layout: str) -> int:
+    try:
+        return ARRAY_LAYOUTS[layout]
+    except (KeyError, TypeError):
+        raise ValueError(f"array samples: unknown layout {layout!r}") from None
+
+
+def array_sample_host(buf, dy: int, dx: int, flip: int,
+                      shape: tuple[int, int, int], crop: tuple[int, int],
+                      scale, bias, dst_dtype: int,
+                      layout: str = "NCHW") -> bytes:
+    """One whole sample (H*W*C uint8 bytes in `buf`) on the host with the
+    routine the array_samples kernel uses: the bytes of its dense C*h*w
+    output (arguments as in Arena.array_samples)."""
+    return load().array_sample_host(buf, dy, dx, flip, tuple(shape),
+                                    tuple(crop), [float(v) for v in scale],
+                                    [float(v) for v in bias], dst_dtype,
+                                    array_layout_code(layout))
 
 
 def token_docs(device: int, x_ptr: int, rows: int, seq_len: int, dtype: int,

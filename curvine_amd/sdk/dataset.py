@@ -22,6 +22,10 @@ HBM tier:
   into rows (`pack_segments`): x, targets masked at document ends, position
   ids, document ids and cu_seqlens from one kernel launch per batch.
 
+* `CurvineArrayLoader` — fixed-shape uint8 image arrays in .npy files:
+  samples become one cropped, flipped, normalised float tensor per batch
+  (NCHW or NHWC) in one kernel launch, with labels on request.
+
 Multiprocess loading: pass ``worker_init_fn=curvine_worker_init`` so each
 DataLoader worker builds its own client connection (connections must not
 be shared across fork).
@@ -843,6 +847,399 @@ class CurvinePackedTokenLoader:
             if "cu_seqlens" in docs:
                 docs["max_seqlen"] = max_seqlen
             yield x, y, docs
+
+    def close(self) -> None:
+        for r in self._readers:
+            r.close()
+        self._readers = []
+        self._fs.shutdown()
+
+
+# ---------------------------------------------------------------------------
+# Array files: fixed-shape uint8 image arrays kept as .npy ([N, H, W, C] or
+# [N, H, W]), the preprocessed-shard format of image, frame and patch
+# datasets.  For HBM-tier files one array_samples_kernel launch per batch
+# reads each sample's crop once from the arena and writes the normalised
+# float tensor in its final layout; no raw-byte tensor, no f32 temporary, no
+# per-sample crop and flip launches.
+# ---------------------------------------------------------------------------
+
+NPY_MAGIC = b"\x93NUMPY"
+NPY_PROBE = 4096          # bytes read first when looking for a header
+
+
+def _npy_header(buf):
+    """(header_bytes, shape, descr, fortran_order) of the .npy file that
+    begins with `buf`, format version 1.0, 2.0 or 3.0; InvalidArgument when
+    `buf` ends inside the header, Unsupported for anything that is not such
+    a header."""
+    import ast
+    import struct
+
+    from curvine_amd import errors as err
+    buf = bytes(buf)
+    if len(buf) < 8 and NPY_MAGIC.startswith(buf[:6]):
+        raise err.InvalidArgument("npy header: file ends inside the header")
+    if buf[:6] != NPY_MAGIC:
+        raise err.Unsupported("npy header: not a .npy file")
+    version = (buf[6], buf[7])
+    if version == (1, 0):
+        pre, fmt = 10, "<H"
+    elif version in ((2, 0), (3, 0)):
+        pre, fmt = 12, "<I"
+    else:
+        raise err.Unsupported(f"npy header: format version {version}")
+    if len(buf) < pre:
+        raise err.InvalidArgument("npy header: file ends inside the header")
+    hlen = struct.unpack_from(fmt, buf, 8)[0]
+    if len(buf) < pre + hlen:
+        raise err.InvalidArgument(
+            f"npy header: {pre + hlen} header bytes, {len(buf)} given")
+    text = buf[pre:pre + hlen].decode("utf-8" if version[0] == 3
+                                      else "latin1")
+    try:
+        d = ast.literal_eval(text)
+        shape, descr = tuple(d["shape"]), d["descr"]
+        fortran = bool(d["fortran_order"])
+        if not all(isinstance(n, int) and n >= 0 for n in shape):
+            raise ValueError(shape)
+    except Exception:  # noqa: BLE001 - whatever a malformed dict raises
+        raise err.Unsupported("npy header: malformed dictionary") from None
+    return pre + hlen, shape, descr, fortran
+
+
+def parse_npy_header(buf):
+    """Header of an image-array .npy file: (header_bytes, shape, descr,
+    fortran_order) from the file's first bytes.  Only descr '|u1', C order
+    and a 3-d [N, H, W] or 4-d [N, H, W, C] shape pass; anything else is
+    Unsupported.  `buf` ending inside the header is InvalidArgument."""
+    from curvine_amd import errors as err
+    header_bytes, shape, descr, fortran = _npy_header(buf)
+    if descr != "|u1":
+        raise err.Unsupported(f"npy header: dtype {descr!r}, only '|u1'")
+    if fortran:
+        raise err.Unsupported("npy header: Fortran order")
+    if len(shape) not in (3, 4):
+        raise err.Unsupported(
+            f"npy header: shape {shape}, only [N, H, W] and [N, H, W, C]")
+    return header_bytes, shape, descr, fortran
+
+
+def _pread_npy(reader, length: int, parse):
+    """parse() over the first bytes of a file, the probe widened once to the
+    length a long header asks for."""
+    from curvine_amd import errors as err
+    head = reader.pread(0, min(NPY_PROBE, length))
+    try:
+        return parse(head)
+    except err.InvalidArgument:
+        if len(head) == length:
+            raise
+    import struct
+    want = 12 + struct.unpack_from("<I", head, 8)[0] if head[6] >= 2 \
+        else 10 + struct.unpack_from("<H", head, 8)[0]
+    return parse(reader.pread(0, min(want, length)))
+
+
+def _f32(v: float) -> float:
+    """v rounded once to float32."""
+    import struct
+    return struct.unpack("<f", struct.pack("<f", v))[0]
+
+
+class CurvineArrayLoader:
+    """Batches of image samples: yields x, one contiguous tensor of
+    ``out_dtype`` (float32, float16 or bfloat16) on ``device``, [B, C, h, w]
+    for layout "NCHW" or [B, h, w, C] for "NHWC", fresh every batch and
+    complete when yielded; with ``labels`` it yields (x, labels), labels an
+    int64 tensor on ``device``.
+
+    Each path is a .npy file (format 1.0, 2.0 or 3.0) holding a C-order
+    uint8 array [N, H, W, C] with 1 <= C <= 4, or [N, H, W] read as C = 1;
+    other headers are Unsupported (`parse_npy_header`), files of different
+    H, W, C or shorter than their header promises InvalidArgument.
+
+    ``crop`` = (h, w), or one int for both, defaults to the whole frame.
+    Element [b, c, r, q] is f32(f32(v) * scale[c]) + bias[c] cast to
+    ``out_dtype``, v the source byte at pixel (dy + r, dx + q), or
+    (dy + r, dx + w-1-q) when the sample is flipped; scale[c] =
+    float32(1 / (255 * std[c])) and bias[c] = float32(-mean[c] / std[c])
+    (``loader.scale``, ``loader.bias``; mean defaults to 0 and std to 1, so
+    the default maps bytes to [0, 1]).
+
+    The global list is the files' samples in the order of ``paths``, or
+    with ``shuffle`` that list under random.Random(seed + epoch).shuffle
+    (``set_epoch``); it is cut to a multiple of ``world`` and rank r takes
+    order[r::world].  The same Random then draws, for every position of the
+    global list in turn, dy = randrange(H-h+1) and dx = randrange(W-w+1)
+    when ``random_crop`` and flip = randrange(2) when ``random_flip``, so
+    every rank derives the same table; without ``random_crop`` the crop is
+    centred, dy = (H-h)//2 and dx = (W-w)//2.  ``augmentation()`` returns
+    this rank's [(dy, dx, flip)] for the current epoch.  Batches are
+    consecutive groups of ``batch_size``; the short last one is dropped
+    when ``drop_last``.
+
+    ``labels`` is one .npy path per data path, 1-d '<i8' or '<i4' of
+    length N, read once at construction; one index operation per plan puts
+    this rank's labels on ``device`` in order and every batch is a slice.
+
+    HBM-tier files + cuda device = the device kernel; MEM tier + cpu device
+    = its host twin; any sample with a part elsewhere (file tier, MEM tier
+    + cuda device, a hole) goes whole through pread and the host routine.
+    Plans are resolved once per order and replayed; the readers stay open,
+    which pins their blocks, until close()."""
+
+    def __init__(self, conf: ClusterConf, paths: list[str], batch_size: int,
+                 device: str = "cuda:0", out_dtype=None, crop=None,
+                 random_crop: bool = False, random_flip: bool = False,
+                 mean=None, std=None, layout: str = "NCHW", labels=None,
+                 shuffle: bool = False, seed: int = 0,
+                 drop_last: bool = True, rank: int = 0, world: int = 1):
+        import torch
+
+        from curvine_amd import errors as err
+        from curvine_amd import native
+        from curvine_amd.client.filesystem import SyncFs
+        from curvine_amd.client.reader import SyncLocalReader
+        out_dtype = torch.float32 if out_dtype is None else out_dtype
+        dst_dtype = {torch.float32: "F32", torch.float16: "F16",
+                     torch.bfloat16: "BF16"}.get(out_dtype)
+        if dst_dtype is None or not native.array_samples_supported(dst_dtype):
+            raise err.Unsupported(
+                f"array loader: {out_dtype} is not a supported output")
+        if layout not in native.ARRAY_LAYOUTS:
+            raise err.InvalidArgument(
+                f"array loader: unknown layout {layout!r}")
+        if not isinstance(batch_size, int) or batch_size <= 0:
+            raise err.InvalidArgument(
+                "array loader: batch_size must be a positive integer")
+        if world <= 0 or not 0 <= rank < world:
+            raise err.InvalidArgument(
+                f"array loader: rank {rank} of world {world}")
+        if labels is not None and len(labels) != len(paths):
+            raise err.InvalidArgument(
+                "array loader: one labels path per data path")
+        self.device = device
+        self.batch_size = batch_size
+        self.out_dtype = out_dtype
+        self.dst_dtype = dst_dtype
+        self.layout = layout
+        self.random_crop = random_crop
+        self.random_flip = random_flip
+        self.shuffle = shuffle
+        self.seed = seed
+        self.drop_last = drop_last
+        self.rank = rank
+        self.world = world
+        self.epoch = 0
+        self.shape = None              # (H, W, C)
+        self._fs = SyncFs(conf)
+        self._readers = []
+        self._samples = []             # (reader_idx, file_off)
+        self._labels = None            # int64 on the cpu, one per sample
+        self._plans = None             # (order key, batch plans, labels)
+        label_parts = []
+        try:
+            for i, p in enumerate(paths):
+                fb = self._fs.call(self._fs.fs.client.open(p))
+                ridx = len(self._readers)
+                r = SyncLocalReader(fb)
+                self._readers.append(r)
+                length = fb.status.length
+                hb, shp, _descr, _f = _pread_npy(r, length, parse_npy_header)
+                n, hwc = shp[0], tuple(shp[1:]) + (1,) * (4 - len(shp))
+                if not 1 <= hwc[2] <= 4 or 0 in hwc:
+                    raise err.Unsupported(
+                        f"array loader: {p} holds samples of shape {hwc}")
+                if self.shape is None:
+                    self.shape = hwc
+                elif hwc != self.shape:
+                    raise err.InvalidArgument(
+                        f"array loader: {p} holds samples of shape {hwc}, "
+                        f"the files before it {self.shape}")
+                sb = hwc[0] * hwc[1] * hwc[2]
+                if length < hb + n * sb:
+                    raise err.InvalidArgument(
+                        f"array loader: {p} is {length} bytes, its header "
+                        f"promises {hb + n * sb}")
+                self._samples += [(ridx, hb + k * sb) for k in range(n)]
+                if labels is not None:
+                    label_parts.append(self._read_labels(labels[i], n))
+            if self.shape is None:
+                raise err.InvalidArgument("array loader: no files")
+            if labels is not None:
+                self._labels = torch.cat(label_parts)
+            H, W, C = self.shape
+            crop = (H, W) if crop is None else crop
+            crop = (crop, crop) if isinstance(crop, int) else tuple(crop)
+            if len(crop) != 2 or not all(isinstance(v, int) for v in crop) \
+                    or not (1 <= crop[0] <= H and 1 <= crop[1] <= W):
+                raise err.InvalidArgument(
+                    f"array loader: crop {crop} of a {H}x{W} frame")
+            self.crop = crop
+            self.scale, self.bias = self._normalisation(mean, std, C)
+        except Exception:
+            self.close()
+            raise
+
+    @staticmethod
+    def _normalisation(mean, std, C: int):
+        from curvine_amd import errors as err
+
+        def per_channel(v, default):
+            if v is None:
+                return [default] * C
+            if isinstance(v, (int, float)):
+                return [float(v)] * C
+            v = [float(t) for t in v]
+            if len(v) != C:
+                raise err.InvalidArgument(
+                    f"array loader: {len(v)} mean/std values for {C} "
+                    "channels")
+            return v
+        import math
+        mean, std = per_channel(mean, 0.0), per_channel(std, 1.0)
+        if any(s == 0 or not math.isfinite(s) for s in std) or \
+                any(not math.isfinite(m) for m in mean):
+            raise err.InvalidArgument(
+                "array loader: mean and std must be finite, std not zero")
+        scale = tuple(_f32(1.0 / (255.0 * s)) for s in std)
+        bias = tuple(_f32(-m / s) for m, s in zip(mean, std))
+        return scale, bias
+
+    def _read_labels(self, path: str, n: int):
+        """The labels of one data file as an int64 cpu tensor."""
+        import torch
+
+        from curvine_amd import errors as err
+        from curvine_amd.client.reader import SyncLocalReader
+        fb = self._fs.call(self._fs.fs.client.open(path))
+        r = SyncLocalReader(fb)
+        try:
+            length = fb.status.length
+            hb, shp, descr, fortran = _pread_npy(r, length, _npy_header)
+            dt = {"<i8": torch.int64, "<i4": torch.int32}.get(descr)
+            if dt is None or len(shp) != 1:
+                raise err.Unsupported(
+                    f"array loader: labels {path} are {descr!r} {shp}, "
+                    "only 1-d '<i8' and '<i4'")
+            if shp[0] != n:
+                raise err.InvalidArgument(
+                    f"array loader: {shp[0]} labels in {path} for {n} "
+                    "samples")
+            nbytes = n * dt.itemsize
+            raw = r.pread(hb, nbytes)
+            if len(raw) != nbytes:
+                raise err.InvalidArgument(
+                    f"array loader: labels {path} shorter than the header "
+                    "promises")
+            if n == 0:
+                return torch.empty(0, dtype=torch.int64)
+            return torch.frombuffer(bytearray(raw), dtype=dt).to(torch.int64)
+        finally:
+            r.close()
+
+    def set_epoch(self, epoch: int) -> None:
+        self.epoch = epoch
+
+    def _order(self):
+        """This rank's (sample indices, [(dy, dx, flip)]) for the epoch."""
+        import random
+        H, W, _C = self.shape
+        h, w = self.crop
+        order = list(range(len(self._samples)))
+        rng = random.Random(self.seed + self.epoch)
+        if self.shuffle:
+            rng.shuffle(order)
+        aug = []
+        for _ in order:
+            dy, dx, flip = (H - h) // 2, (W - w) // 2, 0
+            if self.random_crop:
+                dy = rng.randrange(H - h + 1)
+                dx = rng.randrange(W - w + 1)
+            if self.random_flip:
+                flip = rng.randrange(2)
+            aug.append((dy, dx, flip))
+        keep = len(order) - len(order) % self.world
+        return order[:keep][self.rank::self.world], \
+            aug[:keep][self.rank::self.world]
+
+    def augmentation(self) -> list[tuple[int, int, int]]:
+        """This rank's (dy, dx, flip) per sample, in the order drawn, for
+        the current epoch."""
+        return self._order()[1]
+
+    @property
+    def num_samples(self) -> int:
+        """Samples this rank draws per epoch."""
+        return len(self._samples) // self.world
+
+    def __len__(self) -> int:
+        n, bs = self.num_samples, self.batch_size
+        return n // bs if self.drop_last else (n + bs - 1) // bs
+
+    def _plan(self, on_dev: bool, dev):
+        """Batch plans with every sample resolved down to arena pieces
+        (valid while the readers stay open), the pieces of one arena merged
+        across files so a batch is one launch, and this rank's labels on
+        the device in order."""
+        import torch
+        order, aug = self._order()
+        H, W, C = self.shape
+        bs = self.batch_size
+        plans = []
+        for b in range(len(self)):
+            batch = order[b * bs:(b + 1) * bs]
+            rows = aug[b * bs:(b + 1) * bs]
+            per_reader: dict[int, list] = {}
+            for row, i in enumerate(batch):
+                ridx, off = self._samples[i]
+                per_reader.setdefault(ridx, []).append((off, row))
+            merged: dict[int, tuple[object, list]] = {}
+            execs = []
+            for ridx, samples in per_reader.items():
+                r = self._readers[ridx]
+                groups, slow = r.resolve_array_samples(samples, H * W * C,
+                                                       on_dev)
+                for arena, pieces in groups:
+                    merged.setdefault(arena.handle, (arena, []))[1].extend(
+                        pieces)
+                if slow or not execs:
+                    execs.append((r, [], slow))
+            execs[0] = (execs[0][0], list(merged.values()), execs[0][2])
+            plans.append((len(batch), rows, execs))
+        labels = None
+        if self._labels is not None:
+            n = sum(p[0] for p in plans)
+            labels = self._labels[torch.tensor(order[:n], dtype=torch.int64)]
+            labels = labels.to(dev)
+        return plans, labels
+
+    def __iter__(self):
+        import torch
+        dev = torch.device(self.device)
+        on_dev = dev.type != "cpu"
+        varies = self.shuffle or self.random_crop or self.random_flip
+        key = (self.epoch if varies else None, on_dev)
+        if self._plans is None or self._plans[0] != key:
+            self._plans = (key, *self._plan(on_dev, dev))
+        _key, plans, labels = self._plans
+        H, W, C = self.shape
+        h, w = self.crop
+        at = 0
+        for n, rows, execs in plans:
+            dims = (n, C, h, w) if self.layout == "NCHW" else (n, h, w, C)
+            x = torch.empty(dims, dtype=self.out_dtype, device=dev)
+            for reader, groups, slow in execs:
+                reader.exec_array_samples(
+                    groups, slow, x.data_ptr(), n, rows, self.shape,
+                    self.crop, self.scale, self.bias, self.dst_dtype,
+                    self.layout, on_dev)
+            if labels is None:
+                yield x
+            else:
+                yield x, labels[at:at + n]
+            at += n
 
     def close(self) -> None:
         for r in self._readers:
