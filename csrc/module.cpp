@@ -920,12 +920,16 @@ static Tiles build_tiles(size_t n_items, Len len, Step step, const char* who) {
   return t;
 }
 
+// most workgroups a tiled kernel (or scale_slots_kernel) is launched with;
+// past it a workgroup strides over tiles blockIdx.x, + TILE_GRID_CAP, ...
+static constexpr uint32_t TILE_GRID_CAP = 8192;
+
 template <class Item> struct DevTiles {
   const Item* items;
   const uint32_t* tile_item;
   const uint64_t* tile_off;
   uint32_t n_tiles;
-  unsigned grid() const { return std::min<uint32_t>(n_tiles, 8192); }
+  unsigned grid() const { return std::min<uint32_t>(n_tiles, TILE_GRID_CAP); }
 };
 
 // carve the three tables (8-byte fields first) and upload them on `s`
@@ -2633,6 +2637,7 @@ PYBIND11_MODULE(_native, m) {
   m.def("crc32c_combine", &crc32c_combine);
   m.attr("CRC_SUB") = CRC_SUB;
   m.attr("CAST_TILE") = CAST_TILE;
+  m.attr("TILE_GRID_CAP") = TILE_GRID_CAP;
   m.attr("TOKEN_TILE") = TOKEN_TILE;
   m.attr("ARRAY_TILE") = ARRAY_TILE;
   m.attr("TOKEN_DOC_CHUNK") = TOKEN_DOC_CHUNK;

@@ -204,7 +204,7 @@ static void stream_typed_run(int device, const std::vector<Seg>& segs,
   CallScratch sc(tiles.room<Seg>(segs.size()) +
                  (slots ? Scratch::room<ScaleSlots>(merged.size()) : 0));
   const ScaleSlots* d_slots = nullptr;
-  unsigned slot_grid = (unsigned)std::min<size_t>(merged.size(), 8192);
+  unsigned slot_grid = (unsigned)std::min<size_t>(merged.size(), TILE_GRID_CAP);
   if (slots) {
     ScaleSlots* up = sc.take<ScaleSlots>(merged.size());
     HIP_CHECK(hipMemcpyAsync(up, merged.data(),
